@@ -20,8 +20,11 @@ The line's `value` is the HEADLINE workload: BASELINE C2 (64 agents x 200 steps
 x 32 obstacles), one population per GPU ("weak" scaling: every rank plans the
 same scene), with -- for N > 1 -- the winner records all-gathered once per tick
 by ncclAllGather (RCCL over xGMI), enqueued by libpmaf_hip.so beside the next
-rollout. The same invocation then times BASELINE's other configurations and
-reports them under "configs" (>= 5 blocks each, same timing rules):
+rollout. A plain run times the headline and nothing else. With --full the same
+invocation also measures the idle-stream set-point latencies, the flop count and
+roofline, the C++ facade latency, the CPU baseline and (N = 1) the emulated C5
+scaling curve, and times BASELINE's other configurations, reported under
+"configs" (>= 5 blocks each, same timing rules):
   C1          static1 scene, 16 agents x 100 steps (per-rank replicas)
   C3          256 agents x 500 steps x 128 obstacles (per-rank replicas)
   C5_sharded  8 goal/obstacle scenes x 1024 agents partitioned over the N ranks,
@@ -35,10 +38,13 @@ reports them under "configs" (>= 5 blocks each, same timing rules):
 --only-headline skips them; --config / --shard / --populations / --dynamic
 select another headline workload (then no sub-configurations are run).
 
-Timing: W warm-up ticks, then blocks of K ticks, each block bracketed by a
-barrier + device synchronisation on both sides; blocks are repeated until
---min-seconds have been timed (and at least --min-blocks blocks) and the
-MEDIAN block (max over ranks per block) is reported.
+Timing: W warm-up ticks, then one block of K ticks, bracketed by a barrier +
+device synchronisation on both sides; with --min-seconds / --min-blocks blocks
+are repeated until that much has been timed and the MEDIAN block (max over
+ranks per block) is reported.
+
+--dump-outputs DIR: after the timed ticks, what the headline's last tick handed
+back (best index, next set-point, costs, predicted paths) goes to DIR/*.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -493,14 +499,18 @@ def run_workload(ctx, spec, args, full):
             if hc is not None:
                 hc["pos"] = np.stack([a["start"] for a in S.dual_arm_scenes()])
 
+    last_best = [None]   # what the last tick returned (--dump-outputs)
+
     def one_tick(o):
         tick_no[0] += 1
         if hc is not None:   # host-coupled C4: this arm's trailing obstacle = the other arm's set-point of the last tick
             lo = hc["coupling"].coupled_obstacles(hc["pos"])
             b = planner.tick(lo[me], dt, cg, ws)
             hc["pos"] = planner.winners_wait()[:, 0, 4:7].copy()   # (the collective is ON the control path here)
-            return b
-        return planner.tick(o if spec["dynamic"] else None, dt, cg, ws)
+        else:
+            b = planner.tick(o if spec["dynamic"] else None, dt, cg, ws)
+        last_best[0] = b
+        return b
 
     def sync_all():
         if part:
@@ -567,6 +577,9 @@ def run_workload(ctx, spec, args, full):
         sync_all()
     elapsed = float(np.median(block_s))
     mine_rec = None
+    if part and spec.get("dump_dir"):
+        write_outputs(spec["dump_dir"], timed_outputs(planner, last_best[0]), "" if world == 1 else "rank%d_" % rank,
+                      DUMP_BUDGET_BYTES // world)
     if part:
         lat = np.concatenate(lat)
         kernel_ms, launches, agent_steps = planner.kernel_stats()     # (launches = the TIMED ones)
@@ -723,10 +736,43 @@ def run_workload(ctx, spec, args, full):
         rec["_idle_lib"] = idle_lib
         rec["_closed_sp"] = closed_sp if (part and not ((coupled or host_coupled) and n_part > 1)) else np.zeros(0)
         rec["_scene"] = sc
-        rec["_P"] = P
-        rec["_transport"] = transport
-        rec["_has_comm"] = comm is not None
     return rec
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files of one run together
+
+
+def timed_outputs(planner, best):
+    """What a caller of the timed path holds after its last tick, per population: the best index and the next set-point
+    (position, velocity) pmaf_tick returned, the costs that tick scored, and the rollout it started (every agent's
+    predicted path and its number of points; points past a path's end are zeroed, they are not part of the result)."""
+    P, N = planner.P, planner.N
+    paths, n = planner.paths()
+    paths = np.asarray(paths, dtype=np.float64).reshape(P, N, -1, 3).copy()
+    n = np.asarray(n).reshape(P, N)
+    paths[np.arange(paths.shape[2])[None, None, :] >= n[:, :, None]] = 0.0
+    return {"best_index": np.asarray(best, dtype=np.float64).reshape(P),
+            "next_position": np.asarray(planner.last_next_pos, dtype=np.float64).reshape(P, 3),
+            "next_velocity": np.asarray(planner.last_next_vel, dtype=np.float64).reshape(P, 3),
+            "costs": np.asarray(planner.costs(), dtype=np.float64).reshape(P, N),
+            "path_points": n.astype(np.float64),
+            "paths": paths}
+
+
+def write_outputs(d, outputs, prefix, budget):
+    """outputs -> d/<prefix><name>.npy (float64). Over `budget` bytes, the paths are cut to a fixed, seeded sample of
+    agents (rows of the population x agent axis), whose indices go into paths_sample_rows.npy."""
+    total = sum(a.nbytes for a in outputs.values())
+    if total > budget:
+        paths = outputs["paths"]
+        rows = paths.shape[0] * paths.shape[1]
+        row_bytes = paths.nbytes // rows
+        keep = max(1, (budget - (total - paths.nbytes)) // (row_bytes + 8))   # (+ its index in paths_sample_rows)
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=min(keep, rows), replace=False))
+        outputs = dict(outputs, paths=paths.reshape(rows, *paths.shape[2:])[idx], paths_sample_rows=idx.astype(np.float64))
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 C5_SCALING_REASON = (
@@ -830,9 +876,10 @@ def build_plan(args, world):
     head_spec = dict(config=args.config, mode="c4" if args.config == "C4" else "shard" if args.shard else "replica",
                      populations=args.populations, dynamic=args.dynamic, total_populations=args.total_populations,
                      lanes_per_agent=args.lanes_per_agent, exchange=not args.no_exchange, steps=args.steps,
-                     warmup=args.warmup, min_seconds=args.min_seconds, min_blocks=args.min_blocks)
+                     warmup=args.warmup, min_seconds=args.min_seconds, min_blocks=args.min_blocks,
+                     dump_dir=args.dump_outputs)
     plan, skipped = [], {}
-    if default_headline and not args.only_headline:
+    if default_headline and args.full and not args.only_headline:
         sst = args.sub_steps or min(args.steps, 50)
         base = dict(populations=1, dynamic=False, total_populations=8, lanes_per_agent=0, exchange=True, steps=sst,
                     warmup=min(args.warmup, 10), min_seconds=args.sub_seconds, min_blocks=max(5, args.min_blocks))
@@ -872,10 +919,12 @@ def plan_budget_s(args, world):
         block = sp["steps"] * tick
         timed = max(sp["min_seconds"] + block, sp["min_blocks"] * block)
         t = 0.5 + sp["warmup"] * tick + timed + 0.002 * max(sp["min_blocks"], timed / max(block, 1e-9))
-        if name == "headline":
+        if name == "headline" and args.full:
             t += 1500 * (tick + 60e-6)
         rows.append((name, t))
         total += t
+    if not args.full:
+        return total, rows
     if world == 1:
         # both oracle builds (budget + >= 3 s of warm-up each), then the task_static1 CPU port (<= 8 s + warm-up)
         total += (args.cpu_seconds + 6.0 + 2.0) + ((min(args.cpu_seconds, 8.0) + 6.0 + 2.0) if plan else 0.0)
@@ -900,10 +949,12 @@ def main():
     ap.add_argument("--no-exchange", action="store_true", help="N > 1: no winner-record all-gather (independent replicas)")
     ap.add_argument("--lanes-per-agent", type=int, default=0)
     ap.add_argument("--dynamic", action="store_true", help="moving obstacles, re-uploaded every tick")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline time budget, warm-up not included (0 = skip)")
-    ap.add_argument("--flop-ticks", type=int, default=24, help="ticks of the instrumented-oracle flop count (0 = skip)")
-    ap.add_argument("--min-blocks", type=int, default=5, help="time at least this many blocks of --steps ticks")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: CPU-baseline time budget, warm-up not included (0 = skip)")
+    ap.add_argument("--flop-ticks", type=int, default=24, help="--full: ticks of the instrumented-oracle flop count (0 = skip)")
+    ap.add_argument("--min-blocks", type=int, default=1,
+                    help="time at least this many blocks of --steps ticks (default 1: --steps ticks are timed)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat blocks of --steps ticks until this much has been timed; the median block is reported")
     ap.add_argument("--distinct-scenes", action="store_true",
                     help="N > 1, weak scaling: rank r plans scene(s) r*P .. r*P+P-1 instead of every rank planning the "
@@ -911,13 +962,20 @@ def main():
     ap.add_argument("--episode", type=int, default=256,
                     help="ticks per episode: the real agent is put back at the start every EPISODE ticks so every "
                          "timed rollout runs its full horizon (stationary workload; 0 = never)")
-    ap.add_argument("--only-headline", action="store_true", help="skip the C1 / C3 / C5-sharded / C4 sub-configurations")
+    ap.add_argument("--only-headline", action="store_true",
+                    help="--full: skip the C1 / C3 / C5-sharded / C4 sub-configurations")
     ap.add_argument("--sub-steps", type=int, default=0, help="ticks per block of the sub-configurations (default min(steps, 50))")
     ap.add_argument("--sub-seconds", type=float, default=0.25, help="minimum timed seconds per sub-configuration")
     ap.add_argument("--time-every", type=int, default=8,
                     help="HIP-event timing on every n-th rollout launch of the timed region (1 = every launch)")
     ap.add_argument("--no-c5-emulation", action="store_true",
-                    help="N = 1: skip the emulated 1/2/4/8-GPU curve of BASELINE C5 (scaling_c5.prediction, ~8 s)")
+                    help="--full, N = 1: skip the emulated 1/2/4/8-GPU curve of BASELINE C5 (scaling_c5.prediction, ~8 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the sub-configurations, the emulated C5 scaling curve, the idle-stream "
+                         "set-point latencies, the flop count and roofline, the C++ facade latency and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last tick handed back (best index, next "
+                         "set-point, costs, predicted paths) as DIR/<name>.npy, float64")
     ap.add_argument("--dry-run", action="store_true",
                     help="start the ranks, build the process group and the exchange communicator, all-gather through it "
                          "once and print the launch plan -- no planner, no GPU work (CPU test of the multi-rank plumbing)")
@@ -961,7 +1019,7 @@ def main():
                               "allgather_of_ranks": got}), flush=True)
         return
     head_spec, plan, skipped = build_plan(args, world)
-    head = run_workload(ctx, head_spec, args, full=True)
+    head = run_workload(ctx, head_spec, args, full=args.full)
 
     subs = {}
     for name, spec in plan:
@@ -971,42 +1029,17 @@ def main():
     if rank == 0:
         subs.update(skipped)
     emu = None
-    if world == 1 and plan and not args.no_c5_emulation:
+    if args.full and world == 1 and plan and not args.no_c5_emulation:
         emu = emulate_c5_scaling(ctx, args)
 
     line = None
     if rank == 0 and "skipped" in head:      # (--config C4 on GPUs whose runtime cannot export fine-grained inboxes)
         line = json.dumps({"metric": "agent_rollouts_per_s", "value": None, "skipped": head["skipped"], "n_gpus": world})
     elif rank == 0:
-        idle, sc, P = head.pop("_idle"), head.pop("_scene"), head.pop("_P")
-        wp_lib, wp_wall = head.pop("_wp")
-        idle_enq, idle_sp = head.pop("_idle_lib")
-        closed_sp = head.pop("_closed_sp")
-        transport, has_comm = head.pop("_transport"), head.pop("_has_comm")
+        P = head["populations_per_gpu"]
+        has_comm = head["allgather_us"] is not None
+        transport = head["allgather_us"]["transport"] if has_comm else None
         N, H, n_obs = head["agents"], head["horizon"], head["obstacles"] + 1
-        kernel_name, avg_kernel_s = head["kernel"], head["avg_kernel_us"] * 1e-6
-        steps_per_launch = head["h_eff"] * N * P
-        # exact flop count of this workload from the instrumented oracle
-        fl = measured_flops(ctx.pkg, sc, args.flop_ticks) if args.flop_ticks > 0 else {"error": "skipped"}
-        if "flops_per_agent_step" in fl:
-            flops_step, flop_src = fl["flops_per_agent_step"], "measured"
-        else:
-            M = n_obs - 1   # SURVEY 8(d) estimate as the fall-back
-            flops_step, flop_src = 110 + 47 * M + 12 * M + 65 * (M / 4.0), "SURVEY 8(d) estimate (flop count unavailable)"
-        flops = flops_step * steps_per_launch
-        # HBM traffic per launch of this kernel from the committed PMC passes (tools/gpu_prof.sh +
-        # tools/traffic_from_pmc.py); PMC counters cannot be collected from inside the timed run itself
-        traffic = traffic_src = pmc = None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-            key = "%s%s:%s" % (args.config, "" if P == 1 else "x%d" % P, kernel_name)
-            if key in tj and not args.dynamic:
-                traffic = tj[key]["traffic_bytes_per_launch"]
-                traffic_src = "profiles/traffic.json (rocprofv3 --pmc passes of this command, NOT this run): " + \
-                              tj[key].get("source", "")
-                pmc = {k: tj[key].get(k) for k in ("valu_active_frac_of_wave_cycles", "valu_insts_per_launch", "waves_per_launch")}
-        except (OSError, ValueError, KeyError):
-            traffic = None
         out = {
             "metric": "agent_rollouts_per_s", "value": head["rollouts_per_s"], "unit": "rollouts/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1033,98 +1066,128 @@ def main():
             "agent_steps_per_s": head["agent_steps_per_s"],
             "h_eff": head["h_eff"],
             "tick_latency_us": head["tick_latency_us"],
-            "setpoint_latency_us": None if not idle.size else {
-                "median": float(np.median(idle) * 1e6), "p90": float(np.percentile(idle, 90) * 1e6),
-                "p99": float(np.percentile(idle, 99) * 1e6), "max": float(np.max(idle) * 1e6), "n": int(idle.size),
-                "in_library": None if not idle_sp.size else {
-                    "median": float(np.median(idle_sp)), "p90": float(np.percentile(idle_sp, 90)),
-                    "p99": float(np.percentile(idle_sp, 99)), "max": float(np.max(idle_sp)),
-                    "enqueue_median": float(np.median(idle_enq)), "enqueue_p99": float(np.percentile(idle_enq, 99)),
-                    "note": "the same calls on the library's own clock (pmaf_get_tick_times_us): entry of pmaf_tick -> "
-                            "set-point on the host; enqueue = both launches handed to the stream"},
-                "closed_loop_in_library": None if not closed_sp.size else {
-                    "median": float(np.median(closed_sp)), "p90": float(np.percentile(closed_sp, 90)),
-                    "p99": float(np.percentile(closed_sp, 99)), "n": int(closed_sp.size),
-                    "note": "pmaf_set_real_position(measured) in front of every pmaf_tick (the node with open_loop: false): the "
-                            "position rides in pinned memory into the manager kernel -- no stream sync, no copy command"},
-                "note": "tick issued on an idle stream: host call -> best index + next set-point "
-                        "on the host (the new rollout then runs asynchronously); measured around the ctypes call"},
-            "tick_with_winner_path_us": None if not wp_lib.size else {
-                "median": float(np.median(wp_lib)), "p90": float(np.percentile(wp_lib, 90)),
-                "p99": float(np.percentile(wp_lib, 99)), "max": float(np.max(wp_lib)), "n": int(wp_lib.size),
-                "around_the_ctypes_calls": {"median": float(np.median(wp_wall) * 1e6), "p99": float(np.percentile(wp_wall, 99) * 1e6)},
-                "path_bytes": int((H + 1) * 24),
-                "note": "SURVEY 8(d) tick latency: entry of pmaf_tick -> best index, set-point AND the selected agent's "
-                        "scored path on the host (mapped pinned memory written by the manager kernel, no copy of the "
-                        "other agents' paths); library clock, tick issued on an idle stream"},
             "allgather_us": head["allgather_us"],
             "header_exchange_us": head["header_exchange_us"],
-            "roofline": {"bound": "hbm", "achieved": head["hbm_achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": head["hbm_frac"], "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernel_name,
-                         "avg_kernel_us": head["avg_kernel_us"],
-                         "kernel_timing": head["kernel_timing"],
-                         "algorithmic_bytes_per_launch": head["algorithmic_bytes_per_launch"],
-                         "note": "FP64-VALU/latency-bound ODE integration; HBM fraction is structurally tiny "
-                                 "(SURVEY.md 8d): see fp64_valu"},
-            "fp64_valu": {"achieved_tflops": flops / avg_kernel_s / 1e12, "peak_tflops": FP64_VALU_PEAK_TF,
-                          "frac": flops / avg_kernel_s / 1e12 / FP64_VALU_PEAK_TF,
-                          "flops_per_agent_step": flops_step, "flops_source": flop_src,
-                          "flops_per_agent_step_measured": fl.get("flops_per_agent_step"),
-                          "in_shell_step_fraction": fl.get("in_shell_step_fraction"),
-                          "flop_count": fl,
-                          "pmc": pmc, "pmc_source": traffic_src},
         }
-        if subs:
-            out["configs"] = subs
-        c5 = subs.get("C5_sharded")
-        if c5 and "rollouts_per_s" in c5:
-            # BASELINE config 5's STRONG-scaling record, lifted to the top level beside the weak-scaling `value` (C2, one
-            # population per GPU, ~N x by construction) so that a reader of the 1/2/4/8-GPU lines finds the scaling
-            # statement SURVEY 8(e) asks for without digging through `configs`
-            sc5 = {"read_this_for_scaling": "`value` is BASELINE C2 replicated per GPU (weak scaling: the same 64-agent scene on every "
-                                            "GPU). The scaling record of BASELINE config 5 (8 scenes x 1024 agents, strong scaling) is THIS block.",
-                   "workload": c5["workload"], "scaling": "strong", "n_gpus": world,
-                   "measured": {"rollouts_per_s": c5["rollouts_per_s"], "ms_per_tick": c5["ms_per_tick"],
-                                "avg_kernel_us": c5["avg_kernel_us"], "populations_per_gpu": c5["populations_per_gpu"],
-                                "lanes_per_agent": c5["lanes_per_agent"], "allgather_us": c5.get("allgather_us"),
-                                # SURVEY 8(e)'s scaling report in one place: aggregate rollouts/s and ms per tick above, the
-                                # all-gather beside them, per-GPU tick latency and kernel time here, efficiency below
-                                "per_gpu_tick_us": c5["tick_latency_us"]["per_rank_median"],
-                                "per_gpu_kernel_us": c5["per_rank_kernel_us"]},
-                   "reason": C5_SCALING_REASON}
-            one = subs.get("C5_one_gpu")
-            if one and "rollouts_per_s" in one:
-                sc5["one_gpu_same_job"] = {"rollouts_per_s": one["rollouts_per_s"], "ms_per_tick": one["ms_per_tick"],
-                                           "avg_kernel_us": one["avg_kernel_us"], "lanes_per_agent": one["lanes_per_agent"]}
-                sc5["measured"]["speedup_vs_one_gpu_same_job"] = c5["rollouts_per_s"] / one["rollouts_per_s"]
-                sc5["measured"]["efficiency_vs_one_gpu_same_job"] = c5["rollouts_per_s"] / one["rollouts_per_s"] / world
-            if emu is not None:
-                sc5["prediction"] = emu
-                c5["predicted_by_n"] = emu["predicted_by_n"]
+        if args.full:
+            idle, sc = head.pop("_idle"), head.pop("_scene")
+            wp_lib, wp_wall = head.pop("_wp")
+            idle_enq, idle_sp = head.pop("_idle_lib")
+            closed_sp = head.pop("_closed_sp")
+            kernel_name, avg_kernel_s = head["kernel"], head["avg_kernel_us"] * 1e-6
+            steps_per_launch = head["h_eff"] * N * P
+            # exact flop count of this workload from the instrumented oracle
+            fl = measured_flops(ctx.pkg, sc, args.flop_ticks) if args.flop_ticks > 0 else {"error": "skipped"}
+            if "flops_per_agent_step" in fl:
+                flops_step, flop_src = fl["flops_per_agent_step"], "measured"
             else:
-                sc5["prediction"] = committed_c5_prediction()
-            if sc5.get("prediction") and str(world) in sc5["prediction"]["predicted_by_n"]:
-                pr = sc5["prediction"]["predicted_by_n"][str(world)]
-                sc5["measured"]["vs_predicted_ms_per_tick"] = c5["ms_per_tick"] / pr["ms_per_tick"]
-            out["scaling_c5"] = sc5
-        if world == 1 and not args.only_headline:
-            # tick latency where the reference's node would see it: through the C++ facade, open / closed loop / five calls
-            out["cxx_boundary_latency_us"] = cxx_boundary_latency()
-        if args.cpu_seconds > 0 and world == 1:  # reported at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(args.config if args.config in ("C1", "C2", "C3", "C5") else "C2", args.cpu_seconds)
-            ts = subs.get("task_static1")
-            if ts and "rollouts_per_s" in ts:   # the CPU port at the reference's own parallelism: one thread per agent
-                cb = cpu_baseline("task_static1", min(args.cpu_seconds, 8.0))
-                if "error" not in cb:
-                    ts["cpu_port"] = {k: cb[k] for k in ("value", "best", "cores", "unit", "h_eff", "value_1core", "best_1core",
-                                                         "cpu_model", "share_of_repetitions_within_10pct_of_best")}
-                    ts["cpu_port"]["tick_us_best"] = 1e6 * ts["agents"] / cb["best"]
-                    ts["cpu_port"]["gpu_over_cpu_best"] = ts["rollouts_per_s"] / cb["best"]
+                M = n_obs - 1   # SURVEY 8(d) estimate as the fall-back
+                flops_step, flop_src = 110 + 47 * M + 12 * M + 65 * (M / 4.0), "SURVEY 8(d) estimate (flop count unavailable)"
+            flops = flops_step * steps_per_launch
+            # HBM traffic per launch of this kernel from the committed PMC passes (tools/gpu_prof.sh +
+            # tools/traffic_from_pmc.py); PMC counters cannot be collected from inside the timed run itself
+            traffic = traffic_src = pmc = None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+                key = "%s%s:%s" % (args.config, "" if P == 1 else "x%d" % P, kernel_name)
+                if key in tj and not args.dynamic:
+                    traffic = tj[key]["traffic_bytes_per_launch"]
+                    traffic_src = "profiles/traffic.json (rocprofv3 --pmc passes of this command, NOT this run): " + \
+                                  tj[key].get("source", "")
+                    pmc = {k: tj[key].get(k) for k in ("valu_active_frac_of_wave_cycles", "valu_insts_per_launch", "waves_per_launch")}
+            except (OSError, ValueError, KeyError):
+                traffic = None
+            out.update({
+                "setpoint_latency_us": None if not idle.size else {
+                    "median": float(np.median(idle) * 1e6), "p90": float(np.percentile(idle, 90) * 1e6),
+                    "p99": float(np.percentile(idle, 99) * 1e6), "max": float(np.max(idle) * 1e6), "n": int(idle.size),
+                    "in_library": None if not idle_sp.size else {
+                        "median": float(np.median(idle_sp)), "p90": float(np.percentile(idle_sp, 90)),
+                        "p99": float(np.percentile(idle_sp, 99)), "max": float(np.max(idle_sp)),
+                        "enqueue_median": float(np.median(idle_enq)), "enqueue_p99": float(np.percentile(idle_enq, 99)),
+                        "note": "the same calls on the library's own clock (pmaf_get_tick_times_us): entry of pmaf_tick -> "
+                                "set-point on the host; enqueue = both launches handed to the stream"},
+                    "closed_loop_in_library": None if not closed_sp.size else {
+                        "median": float(np.median(closed_sp)), "p90": float(np.percentile(closed_sp, 90)),
+                        "p99": float(np.percentile(closed_sp, 99)), "n": int(closed_sp.size),
+                        "note": "pmaf_set_real_position(measured) in front of every pmaf_tick (the node with open_loop: false): the "
+                                "position rides in pinned memory into the manager kernel -- no stream sync, no copy command"},
+                    "note": "tick issued on an idle stream: host call -> best index + next set-point "
+                            "on the host (the new rollout then runs asynchronously); measured around the ctypes call"},
+                "tick_with_winner_path_us": None if not wp_lib.size else {
+                    "median": float(np.median(wp_lib)), "p90": float(np.percentile(wp_lib, 90)),
+                    "p99": float(np.percentile(wp_lib, 99)), "max": float(np.max(wp_lib)), "n": int(wp_lib.size),
+                    "around_the_ctypes_calls": {"median": float(np.median(wp_wall) * 1e6), "p99": float(np.percentile(wp_wall, 99) * 1e6)},
+                    "path_bytes": int((H + 1) * 24),
+                    "note": "SURVEY 8(d) tick latency: entry of pmaf_tick -> best index, set-point AND the selected agent's "
+                            "scored path on the host (mapped pinned memory written by the manager kernel, no copy of the "
+                            "other agents' paths); library clock, tick issued on an idle stream"},
+                "roofline": {"bound": "hbm", "achieved": head["hbm_achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": head["hbm_frac"], "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": kernel_name,
+                             "avg_kernel_us": head["avg_kernel_us"],
+                             "kernel_timing": head["kernel_timing"],
+                             "algorithmic_bytes_per_launch": head["algorithmic_bytes_per_launch"],
+                             "note": "FP64-VALU/latency-bound ODE integration; HBM fraction is structurally tiny "
+                                     "(SURVEY.md 8d): see fp64_valu"},
+                "fp64_valu": {"achieved_tflops": flops / avg_kernel_s / 1e12, "peak_tflops": FP64_VALU_PEAK_TF,
+                              "frac": flops / avg_kernel_s / 1e12 / FP64_VALU_PEAK_TF,
+                              "flops_per_agent_step": flops_step, "flops_source": flop_src,
+                              "flops_per_agent_step_measured": fl.get("flops_per_agent_step"),
+                              "in_shell_step_fraction": fl.get("in_shell_step_fraction"),
+                              "flop_count": fl,
+                              "pmc": pmc, "pmc_source": traffic_src},
+            })
+            if subs:
+                out["configs"] = subs
+            c5 = subs.get("C5_sharded")
+            if c5 and "rollouts_per_s" in c5:
+                # BASELINE config 5's STRONG-scaling record, lifted to the top level beside the weak-scaling `value` (C2, one
+                # population per GPU, ~N x by construction) so that a reader of the 1/2/4/8-GPU lines finds the scaling
+                # statement SURVEY 8(e) asks for without digging through `configs`
+                sc5 = {"read_this_for_scaling": "`value` is BASELINE C2 replicated per GPU (weak scaling: the same 64-agent scene on every "
+                                                "GPU). The scaling record of BASELINE config 5 (8 scenes x 1024 agents, strong scaling) is THIS block.",
+                       "workload": c5["workload"], "scaling": "strong", "n_gpus": world,
+                       "measured": {"rollouts_per_s": c5["rollouts_per_s"], "ms_per_tick": c5["ms_per_tick"],
+                                    "avg_kernel_us": c5["avg_kernel_us"], "populations_per_gpu": c5["populations_per_gpu"],
+                                    "lanes_per_agent": c5["lanes_per_agent"], "allgather_us": c5.get("allgather_us"),
+                                    # SURVEY 8(e)'s scaling report in one place: aggregate rollouts/s and ms per tick above, the
+                                    # all-gather beside them, per-GPU tick latency and kernel time here, efficiency below
+                                    "per_gpu_tick_us": c5["tick_latency_us"]["per_rank_median"],
+                                    "per_gpu_kernel_us": c5["per_rank_kernel_us"]},
+                       "reason": C5_SCALING_REASON}
+                one = subs.get("C5_one_gpu")
+                if one and "rollouts_per_s" in one:
+                    sc5["one_gpu_same_job"] = {"rollouts_per_s": one["rollouts_per_s"], "ms_per_tick": one["ms_per_tick"],
+                                               "avg_kernel_us": one["avg_kernel_us"], "lanes_per_agent": one["lanes_per_agent"]}
+                    sc5["measured"]["speedup_vs_one_gpu_same_job"] = c5["rollouts_per_s"] / one["rollouts_per_s"]
+                    sc5["measured"]["efficiency_vs_one_gpu_same_job"] = c5["rollouts_per_s"] / one["rollouts_per_s"] / world
+                if emu is not None:
+                    sc5["prediction"] = emu
+                    c5["predicted_by_n"] = emu["predicted_by_n"]
                 else:
-                    ts["cpu_port"] = cb
-        else:
-            out["cpu_baseline"] = None
+                    sc5["prediction"] = committed_c5_prediction()
+                if sc5.get("prediction") and str(world) in sc5["prediction"]["predicted_by_n"]:
+                    pr = sc5["prediction"]["predicted_by_n"][str(world)]
+                    sc5["measured"]["vs_predicted_ms_per_tick"] = c5["ms_per_tick"] / pr["ms_per_tick"]
+                out["scaling_c5"] = sc5
+            if world == 1 and not args.only_headline:
+                # tick latency where the reference's node would see it: through the C++ facade, open / closed loop / five calls
+                out["cxx_boundary_latency_us"] = cxx_boundary_latency()
+            if args.cpu_seconds > 0 and world == 1:  # reported at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(args.config if args.config in ("C1", "C2", "C3", "C5") else "C2", args.cpu_seconds)
+                ts = subs.get("task_static1")
+                if ts and "rollouts_per_s" in ts:   # the CPU port at the reference's own parallelism: one thread per agent
+                    cb = cpu_baseline("task_static1", min(args.cpu_seconds, 8.0))
+                    if "error" not in cb:
+                        ts["cpu_port"] = {k: cb[k] for k in ("value", "best", "cores", "unit", "h_eff", "value_1core", "best_1core",
+                                                             "cpu_model", "share_of_repetitions_within_10pct_of_best")}
+                        ts["cpu_port"]["tick_us_best"] = 1e6 * ts["agents"] / cb["best"]
+                        ts["cpu_port"]["gpu_over_cpu_best"] = ts["rollouts_per_s"] / cb["best"]
+                    else:
+                        ts["cpu_port"] = cb
+            else:
+                out["cpu_baseline"] = None
         line = json.dumps(out)
 
     def flush_all():

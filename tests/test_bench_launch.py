@@ -46,7 +46,8 @@ def test_gpus_8_dry_run_and_the_plan_budget():
     """the machine the driver scales on has 8 GPUs: `--gpus 8` without a launcher starts eight ranks (gloo, one device
     hook), the exchange communicator spans all eight, and the launch plan of the default command stays inside one
     minute of GPU-side time by construction of its sub-configuration budgets (bench.plan_budget_s)"""
-    r = _run(["--gpus", "8", "--dry-run", "--steps", "20", "--warmup", "5"], PMAF_BENCH_BACKEND="gloo", PMAF_BENCH_SINGLE_DEVICE="1")
+    r = _run(["--gpus", "8", "--dry-run", "--full", "--steps", "20", "--warmup", "5"], PMAF_BENCH_BACKEND="gloo",
+             PMAF_BENCH_SINGLE_DEVICE="1")
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 8 and out["collective_world"] == 8
@@ -72,7 +73,7 @@ def test_plan_is_the_same_code_path_for_every_world_size():
     bench = importlib.import_module("bench")
     ns = dict(config="C2", shard=False, populations=1, dynamic=False, lanes_per_agent=0, total_populations=8, no_exchange=False,
               steps=20, warmup=5, min_seconds=1.0, min_blocks=5, only_headline=False, sub_steps=0, sub_seconds=0.25,
-              cpu_seconds=11.0, flop_ticks=24)
+              cpu_seconds=11.0, flop_ticks=24, full=True, dump_outputs=None)
     plans = {w: bench.build_plan(argparse.Namespace(**ns), w) for w in (1, 2, 3, 4, 8)}
     for w, (head, plan, skipped) in plans.items():
         assert head == plans[1][0]
@@ -90,6 +91,42 @@ def test_plan_is_the_same_code_path_for_every_world_size():
     # the default flags (no --steps / --warmup): still minutes, not more
     ns2 = dict(ns, steps=2000, warmup=100)
     assert bench.plan_budget_s(argparse.Namespace(**ns2), 1)[0] < 180.0
+
+
+def test_plain_run_times_the_headline_only():
+    """without --full the launch plan is the headline alone: --steps ticks in one block after --warmup, no
+    sub-configurations, and a time budget of the headline's own (no CPU baseline, flop count or C5 emulation)"""
+    r = _run(["--gpus", "2", "--dry-run", "--steps", "20", "--warmup", "5"], PMAF_BENCH_BACKEND="gloo", PMAF_BENCH_SINGLE_DEVICE="1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["plan"] == [] and out["plan_skipped"] == []
+    head = out["headline"]
+    assert head["steps"] == 20 and head["warmup"] == 5 and head["min_blocks"] == 1 and head["min_seconds"] == 0.0
+    assert [n for n, _ in out["budget_rows"]] == ["headline"] and out["budget_s"] < 2.0
+
+
+def test_dump_outputs_fit_the_budget(tmp_path):
+    """--dump-outputs: float64 .npy files; an output over the byte budget keeps a fixed, seeded sample of agents' paths"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    P, N, cap = 2, 50, 11
+    outs = {"best_index": np.array([3.0, 7.0]), "paths": np.arange(P * N * cap * 3, dtype=np.float64).reshape(P, N, cap, 3)}
+    bench.write_outputs(str(tmp_path / "all"), dict(outs), "", 1 << 20)
+    assert sorted(os.listdir(tmp_path / "all")) == ["best_index.npy", "paths.npy"]
+    assert (np.load(tmp_path / "all" / "paths.npy") == outs["paths"]).all()
+    budget = 16 + 40 * cap * 3 * 8
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), dict(outs), "rank0_", budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["rank0_best_index.npy", "rank0_paths.npy", "rank0_paths_sample_rows.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= budget
+    rows = np.load(tmp_path / "a" / "rank0_paths_sample_rows.npy")
+    got = np.load(tmp_path / "a" / "rank0_paths.npy")
+    assert got.dtype == np.float64 and 0 < rows.size < P * N and (np.diff(rows) > 0).all()
+    assert (got == outs["paths"].reshape(P * N, cap, 3)[rows.astype(int)]).all()
+    for f in files:   # the same sample every run
+        assert (np.load(tmp_path / "a" / f) == np.load(tmp_path / "b" / f)).all()
 
 
 def test_kernel_names_follow_the_librarys_routing():

@@ -2,8 +2,10 @@
 the facade's obstacle.h / cf_manager.h must shadow the reference's headers for `panda_bimanual_control_node` ONLY --
 src/obstacle.cpp and src/cf_agent.cpp are also compiled into dual_panda_costp_controller, vrep_interface,
 dynamic_obstacle_node and vision_interface_node (B/CMakeLists.txt:105-116, :165-175, :191-195, :210-214), which must
-keep the reference's headers. CPU tests; the ones that read /root/reference skip themselves where it is absent (the
-GPU box)."""
+keep the reference's headers. CPU tests; what they need of the reference package -- its CMake targets, header, message
+and service names and the include lines of its files -- is the fixture tests/golden/reference_package.json
+(tests/golden/make_reference_package.py)."""
+import json
 import os
 import re
 import subprocess
@@ -11,14 +13,10 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-B = "/root/reference/src/bimanual_planning_ros"
+REF = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_package.json")))
 NODE = "panda_bimanual_control_node"
 REPLACED_SOURCES = {"src/obstacle.cpp", "src/cf_agent.cpp", "src/cf_manager.cpp", "src/helper_functions.cpp"}
 FACADE_SHADOWS = {"cf_manager.h", "obstacle.h"}   # the only header names the facade may share with B/include
-
-needs_reference = pytest.mark.skipif(not os.path.exists(os.path.join(B, "CMakeLists.txt")),
-                                     reason="reference checkout not present (GPU box)")
-
 
 def cmake_commands(text):
     """[(command, [arguments])] of a CMake file / snippet (comments stripped; no nested parentheses in this package)"""
@@ -57,9 +55,8 @@ def test_recipe_is_scoped_to_the_planner_node():
     assert props and props[0][0] == "pmaf_hip" and props[0][-1].endswith("predictive-multi-agent-framework_amd/lib/libpmaf_hip.so")
 
 
-@needs_reference
 def test_recipe_source_list_is_the_reference_list_minus_the_replaced_units():
-    ref = targets_with_sources(cmake_commands(open(os.path.join(B, "CMakeLists.txt")).read()))
+    ref = targets_with_sources(REF["cmake_commands"])
     mine = targets_with_sources(cmake_commands(recipe_snippet()))
     assert set(mine) == {NODE, "pmaf_hip"} and mine["pmaf_hip"] == []   # (the IMPORTED library has no sources)
     assert set(ref[NODE]) - set(mine[NODE]) == REPLACED_SOURCES
@@ -67,86 +64,96 @@ def test_recipe_source_list_is_the_reference_list_minus_the_replaced_units():
     assert set(ref[NODE]) & REPLACED_SOURCES == REPLACED_SOURCES
 
 
-@needs_reference
 def test_other_targets_compiling_obstacle_or_agent_keep_the_reference_headers():
     """every target of the reference package that compiles obstacle.cpp / cf_agent.cpp / cf_manager.cpp, and which of
     them the recipe touches (the node, nothing else)"""
-    ref = targets_with_sources(cmake_commands(open(os.path.join(B, "CMakeLists.txt")).read()))
+    ref = targets_with_sources(REF["cmake_commands"])
     users = {t for t, srcs in ref.items() if set(srcs) & {"src/obstacle.cpp", "src/cf_agent.cpp", "src/cf_manager.cpp"}}
     assert users == {NODE, "dual_panda_costp_controller", "vrep_interface", "dynamic_obstacle_node", "vision_interface_node"}
     touched = {a[0] for c, a in cmake_commands(recipe_snippet()) if c.startswith("target_") or c == "add_executable"}
     assert touched == {NODE}
     # the directory-wide include path of the package is `include` alone (:84-86): the recipe adds to the node's own list
-    dirwide = [a for c, a in cmake_commands(open(os.path.join(B, "CMakeLists.txt")).read()) if c == "include_directories"]
+    dirwide = [a for c, a in REF["cmake_commands"] if c == "include_directories"]
     assert dirwide == [["include"]]
     md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for t in users - {NODE}:
         assert t in md, "INTEGRATION.md must say that %s keeps the reference's headers" % t
 
 
-def _resolve(name, search):
-    for d in search:
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return p
-    return None
+FACADE_INC = os.path.join(ROOT, "include")
 
 
-@needs_reference
+def _resolve(name):
+    """<name> with the node's include order [PMAF/include, B/include]: a path of the facade, or the reference's file as
+    the fixture names it (include/<name>), or None (not in either: a generated message header)"""
+    p = os.path.join(FACADE_INC, name)
+    if os.path.exists(p):
+        return p
+    return "include/" + name if "include/" + name in REF["includes"] else None
+
+
+def _includes(f):
+    if f.startswith(FACADE_INC):
+        return re.findall(r'#include\s*[<"](bimanual_planning_ros/[\w.]+)[>"]', open(f).read())
+    return REF["includes"][f]
+
+
 def test_node_include_set_resolves_to_the_facade_for_two_headers_only():
     """the node target's include order [PMAF/include, B/include]: walking the <bimanual_planning_ros/...> includes of
     the node's remaining sources, cf_manager.h (panda_bimanual_control.h:6) and obstacle.h (:9) come from the facade,
     everything else from the reference, and neither cf_agent.h nor helper_functions.h -- whose translation units the
     recipe drops -- is reached"""
-    search = [os.path.join(ROOT, "include"), os.path.join(B, "include")]
     mine = targets_with_sources(cmake_commands(recipe_snippet()))[NODE]
     facade_names = set(os.listdir(os.path.join(ROOT, "include", "bimanual_planning_ros")))
-    ref_names = set(os.listdir(os.path.join(B, "include", "bimanual_planning_ros")))
+    ref_names = set(REF["headers"])
     assert facade_names & ref_names == FACADE_SHADOWS
-    seen, from_facade, queue = set(), set(), [os.path.join(B, s) for s in mine]
+    seen, from_facade, queue = set(), set(), list(mine)
     generated = set()   # message headers (catkin generates them: Position.h, Obstacles.h ...)
     while queue:
         f = queue.pop()
         if f in seen:
             continue
         seen.add(f)
-        for m in re.finditer(r'#include\s*[<"](bimanual_planning_ros/[\w.]+)[>"]', open(f).read()):
-            r = _resolve(m.group(1), search)
+        for name in _includes(f):
+            r = _resolve(name)
             if r is None:
-                generated.add(m.group(1))
+                generated.add(name)
                 continue
-            if r.startswith(search[0]):
+            if r.startswith(FACADE_INC):
                 from_facade.add(os.path.basename(r))
             queue.append(r)
     assert from_facade == FACADE_SHADOWS, from_facade
     reached = {os.path.basename(f) for f in seen}
     assert "panda_bimanual_control.h" in reached
     assert not ({"cf_agent.h", "helper_functions.h"} & reached), reached
-    msgs = {os.path.splitext(f)[0] for f in os.listdir(os.path.join(B, "msg"))} | {os.path.splitext(f)[0] for f in os.listdir(os.path.join(B, "srv"))}
+    msgs = set(REF["messages"]) | set(REF["services"])
     assert {os.path.splitext(os.path.basename(g))[0] for g in generated} <= msgs, generated
 
 
-@needs_reference
-def test_compiler_picks_the_facade_with_the_node_include_order():
+def test_compiler_picks_the_facade_with_the_node_include_order(tmp_path):
     """the same through a compiler: `g++ -M` of the two includes the node header makes, with the node target's include
     order and the API-shape Eigen declarations (tests/cpp/eigen_api_check; this image has no Eigen3), lists the facade's
-    headers and none of the reference's"""
+    headers and none of the reference's -- whose include/ is stood in for by headers of the same names that stop the
+    compile when they are reached"""
     chk = os.path.join(ROOT, "tests", "cpp", "eigen_api_check")
+    B_include = tmp_path / "include"
+    (B_include / "bimanual_planning_ros").mkdir(parents=True)
+    for h in REF["headers"]:
+        (B_include / "bimanual_planning_ros" / h).write_text('#error "the reference\'s %s was reached"\n' % h)
     src = "#include <bimanual_planning_ros/cf_manager.h>\n#include <bimanual_planning_ros/obstacle.h>\n"
     r = subprocess.run(["g++", "-std=c++17", "-M", "-DPMAF_USE_EIGEN", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(B, "include"), "-I" + chk, "-x", "c++", "-"], input=src.encode(), capture_output=True)
+                        "-I" + str(B_include), "-I" + chk, "-x", "c++", "-"], input=src.encode(), capture_output=True)
     assert r.returncode == 0, r.stderr.decode()
     deps = r.stdout.decode().replace("\\\n", " ").split()
     ours = [d for d in deps if "bimanual_planning_ros/" in d]
     assert ours and all(os.path.abspath(d).startswith(os.path.join(ROOT, "include")) for d in ours), ours
     # and the node's call forms still compile in that order (syntax only)
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-DPMAF_USE_EIGEN",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(B, "include"), "-I" + chk,
+                        "-I" + os.path.join(ROOT, "include"), "-I" + str(B_include), "-I" + chk,
                         "-I" + os.path.join(chk, "eigen3"), os.path.join(chk, "node_style_caller.cpp")], capture_output=True)
     assert r.returncode == 0, r.stderr.decode()
 
 
-@needs_reference
 def test_recipe_through_cmake_on_a_package_with_the_reference_targets(tmp_path):
     """the recipe run by CMake itself: a package with the reference's targets and source lists (names read from
     B/CMakeLists.txt; the sources are probes that only include <bimanual_planning_ros/obstacle.h>, the package's own
@@ -160,7 +167,7 @@ def test_recipe_through_cmake_on_a_package_with_the_reference_targets(tmp_path):
     import shutil
     if shutil.which("cmake") is None:
         pytest.skip("no cmake")
-    ref = targets_with_sources(cmake_commands(open(os.path.join(B, "CMakeLists.txt")).read()))
+    ref = targets_with_sources(REF["cmake_commands"])
     pkg = tmp_path / "pkg"
     (pkg / "include" / "bimanual_planning_ros").mkdir(parents=True)
     (pkg / "src").mkdir()

@@ -49,10 +49,9 @@ def test_task_loader_on_fixtures(hip_lib):
     assert d["k_circ"] == 0.025 and d["goals"][1]["overrides"] == {"k_circ": 0.015}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/bimanual_planning_ros/config/tasks"),
-                    reason="reference checkout only exists in the build container")
 def test_task_loader_on_the_reference_task_files(hip_lib):
-    files = sorted(glob.glob("/root/reference/src/bimanual_planning_ros/config/tasks/*.yaml"))
+    """the reference package's nine shipped task files, kept verbatim as fixtures (tests/golden/make_reference_package.py)"""
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "reference_tasks", "*.yaml")))
     assert len(files) == 9
     for f in files:
         _check_against_yaml(f)

@@ -574,7 +574,7 @@ def test_bench_self_spawns_its_ranks_and_reports_every_config():
     import subprocess
     env = dict(os.environ, PMAF_BENCH_BACKEND="gloo", PMAF_BENCH_SINGLE_DEVICE="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "3",
                         "--min-seconds", "0.05", "--sub-seconds", "0.02", "--flop-ticks", "0"],
                        capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -640,7 +640,7 @@ def test_bench_one_gpu_line_carries_the_emulated_c5_scaling_curve():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "PMAF_BENCH_FORCE_DIST")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0.1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--min-seconds", "0.1",
                         "--sub-seconds", "0.05", "--cpu-seconds", "0", "--flop-ticks", "0"],
                        capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -678,6 +678,37 @@ def test_bench_rccl_bootstrap_failure_falls_back_to_host_transport():
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["allgather_us"]["n"] >= 20 and out["allgather_us"]["transport"] == "host"
     assert "host transport" in out["config"]["workload"]
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_steps_and_dumps_reproducible_outputs(tmp_path):
+    """the plain command: exactly --steps timed ticks (one block), ms_per_step = that block / steps, no sub-records; and
+    --dump-outputs writes what the last timed tick handed back -- the same bits on a second run with the same arguments"""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "PMAF_BENCH_FORCE_DIST")}
+    outs, lines = [], []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        outs.append({f[:-4]: np.load(os.path.join(str(d), f)) for f in sorted(os.listdir(str(d)))})
+    out = lines[0]
+    assert out["metric"] == "agent_rollouts_per_s" and out["unit"] == "rollouts/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f64" and out["steps"] == 30 and out["value"] > 0
+    assert out["timing"]["blocks"] == 1 and out["timing"]["block_ticks"] == 30
+    assert abs(out["ms_per_step"] * 30 - out["timing"]["timed_s"] * 1e3) < 1e-9
+    assert abs(out["value"] - 64 * 30 / out["timing"]["timed_s"]) < 1e-6 * out["value"]
+    assert "configs" not in out and "cpu_baseline" not in out and "setpoint_latency_us" not in out
+    o = outs[0]
+    assert sorted(o) == ["best_index", "costs", "next_position", "next_velocity", "path_points", "paths"]
+    assert o["paths"].shape == (1, 64, 201, 3) and o["costs"].shape == (1, 64) and o["next_position"].shape == (1, 3)
+    assert all(a.dtype == np.float64 for a in o.values())
+    assert 0 <= o["best_index"][0] < 64 and (o["path_points"] == 201).all() and np.isfinite(o["paths"]).all()
+    for name in o:
+        assert np.array_equal(o[name], outs[1][name]), name
 
 
 @pytest.mark.timeout(600)

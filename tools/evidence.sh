@@ -10,15 +10,15 @@ mkdir -p $O
 PARTS=${@:-bench scaling prof misc variant tests}
 for part in $PARTS; do case $part in
 bench)
-  python bench.py --steps 20 --warmup 5 > $O/bench_c2_driver_flags.json 2> $O/bench.err
-  python bench.py > $O/bench_c2.json 2>> $O/bench.err
-  python bench.py --config C3 --steps 400 --only-headline --cpu-seconds 6 > $O/bench_c3.json 2>> $O/bench.err
-  python bench.py --config C5 --populations 8 --steps 400 --only-headline --cpu-seconds 6 --flop-ticks 2 > $O/bench_c5x8.json 2>> $O/bench.err
-  python bench.py --dynamic --only-headline --cpu-seconds 0 > $O/bench_c2_dynamic.json 2>> $O/bench.err
-  python bench.py --config C5 --populations 2 --steps 400 --only-headline --cpu-seconds 0 --flop-ticks 2 > $O/bench_c5x2.json 2>> $O/bench.err
-  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_2ranks_1gpu_selfspawn.json
-  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 PMAF_BENCH_C4_HOST_COUPLED=1 python bench.py --gpus 2 --config C4 --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c4_2ranks_host_coupled.json
-  PMAF_BENCH_FORCE_DIST=1 MASTER_PORT=29531 python bench.py --only-headline --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c2_rccl_1rank.json
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_c2_driver_flags.json 2> $O/bench.err
+  python bench.py --full > $O/bench_c2.json 2>> $O/bench.err
+  python bench.py --full --config C3 --steps 400 --only-headline --cpu-seconds 6 > $O/bench_c3.json 2>> $O/bench.err
+  python bench.py --full --config C5 --populations 8 --steps 400 --only-headline --cpu-seconds 6 --flop-ticks 2 > $O/bench_c5x8.json 2>> $O/bench.err
+  python bench.py --full --dynamic --only-headline --cpu-seconds 0 > $O/bench_c2_dynamic.json 2>> $O/bench.err
+  python bench.py --full --config C5 --populations 2 --steps 400 --only-headline --cpu-seconds 0 --flop-ticks 2 > $O/bench_c5x2.json 2>> $O/bench.err
+  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 python bench.py --full --gpus 2 --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_2ranks_1gpu_selfspawn.json
+  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 PMAF_BENCH_C4_HOST_COUPLED=1 python bench.py --full --gpus 2 --config C4 --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c4_2ranks_host_coupled.json
+  PMAF_BENCH_FORCE_DIST=1 MASTER_PORT=29531 python bench.py --full --only-headline --cpu-seconds 0 --flop-ticks 0 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c2_rccl_1rank.json
   # the CPU baseline twice more, back to back: does `best` reproduce on this box?
   python oracle/cpu_bench.py --config C2 --budget 12 > $O/cpu_bench_c2_run1.json 2>> $O/bench.err
   python oracle/cpu_bench.py --config C2 --budget 12 > $O/cpu_bench_c2_run2.json 2>> $O/bench.err
@@ -27,8 +27,8 @@ scaling)
   # BASELINE C5's strong-scaling curve emulated on this one GPU (bench.py: emulate_c5_scaling) + what the all-gather of
   # the winner records costs where it can be measured here: RCCL with ONE rank (the enqueue + kernel of ncclAllGather on
   # the exchange stream) and two ranks sharing this GPU over the host transport -> profiles/${R}_scaling_emulated.json
-  PMAF_BENCH_FORCE_DIST=1 MASTER_PORT=29533 python bench.py --config C5 --shard --only-headline --cpu-seconds 0 --flop-ticks 0 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c5_rccl_1rank.json
-  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --config C5 --shard --only-headline --cpu-seconds 0 --flop-ticks 0 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c5shard_2ranks_1gpu_host.json
+  PMAF_BENCH_FORCE_DIST=1 MASTER_PORT=29533 python bench.py --full --config C5 --shard --only-headline --cpu-seconds 0 --flop-ticks 0 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c5_rccl_1rank.json
+  PMAF_BENCH_BACKEND=gloo PMAF_BENCH_SINGLE_DEVICE=1 python bench.py --full --gpus 2 --config C5 --shard --only-headline --cpu-seconds 0 --flop-ticks 0 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 > $O/bench_c5shard_2ranks_1gpu_host.json
   python tools/scaling_emulated.py $O/bench_c2_driver_flags.json $O/bench_c5_rccl_1rank.json $O/bench_c5shard_2ranks_1gpu_host.json $O/bench_c2_rccl_1rank.json > $O/scaling_emulated.json 2>> $O/bench.err
   ;;
 prof)
@@ -50,9 +50,9 @@ misc)
 variant)   # the right-associated library + oracle: the FULL 0-tolerance suite, and the kernel times of both libraries on one box
   PMAF_VARIANT=rassoc python -m pytest tests -m gpu -q -p no:cacheprovider --deselect tests/test_build_variants.py 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -8 > $O/gpu_tests_rassoc.log
   for v in "" rassoc; do for c in C1 C2 C3 C4; do
-    PMAF_VARIANT=$v python bench.py --config $c --only-headline --cpu-seconds 0 --flop-ticks 0 --min-seconds 0.5 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 |
+    PMAF_VARIANT=$v python bench.py --full --config $c --only-headline --cpu-seconds 0 --flop-ticks 0 --min-seconds 0.5 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 |
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-7s %-3s %s %.1f us per launch, %.0f rollouts/s' % ('$v' or 'default', '$c', d['roofline']['kernel'], d['roofline']['avg_kernel_us'], d['value']))"
-  done; PMAF_VARIANT=$v python bench.py --config C5 --populations 8 --only-headline --cpu-seconds 0 --flop-ticks 0 --min-seconds 0.5 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 |
+  done; PMAF_VARIANT=$v python bench.py --full --config C5 --populations 8 --only-headline --cpu-seconds 0 --flop-ticks 0 --min-seconds 0.5 --steps 200 2>> $O/bench.err | grep "^{" | tail -1 |
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-7s %-3s %s %.1f us per launch, %.0f rollouts/s' % ('$v' or 'default', 'C5x8', d['roofline']['kernel'], d['roofline']['avg_kernel_us'], d['value']))"
   done > $O/variant_kernel_times.txt 2>&1
   ;;
