@@ -1,0 +1,211 @@
+"""Every rollout kernel family and arithmetic policy against the independent high-precision reference
+(tests/hp_reference.py), one tick or one stepping call at a time on the HIP path's own fp64 state (tests/hp_shadow.py).
+
+The parity suite holds the strict kernels to the CPU oracle bit for bit and the contracted ones to 1e-5 m end to end;
+here each output is held to the reference's rounding-error bound for the policy's documented per-operation error, and
+each decided branch to the reference's side. launch_config() confirms which kernel ran. Large shapes compare a seeded
+sample of agents (the agents of a rollout are independent). Run with -s to see the per-case report.
+"""
+import numpy as np
+import pytest
+import torch
+
+import hp_edges
+import hp_reference as hp
+import hp_shadow as sh
+
+pytestmark = pytest.mark.gpu
+
+POLICY_KW = {"xact": {}, "ieee": {"ieee_sequences": True}, "fast": {"fast_math": True}, "fma": {"contracted": True}}
+ONE_STEP_MAX_UNDECIDABLE = 0.02
+K_STEP_MAX_UNDECIDABLE = 0.10       # see tests/test_hp_reference.py: the bound of a step near a sphere grows fast
+
+
+def _simds():
+    return torch.cuda.get_device_properties(0).multi_processor_count * 4
+
+
+def _planner(pmaf, scene, policy, lpa=0):
+    return pmaf.PmafPlanner(scene, device=0, mgr_init_pos=scene["start"], lanes_per_agent=lpa, **POLICY_KW[policy])
+
+
+def _sample(n, k, seed=7):
+    if n <= k:
+        return list(range(n))
+    return sorted(np.random.default_rng(seed).choice(n, k, replace=False).tolist())
+
+
+def run_ticks(pmaf, scenes, scene, n_ticks, policy, name, lpa=0, dynamic=False, n_sample=16, expect=None):
+    A = hp.Arith(policy)
+    st = sh.Stats("%s [%s]" % (name, policy))
+    pl = _planner(pmaf, scene, policy, lpa)
+    try:
+        ip = sh.start(pl, scene, init_pos=scene["start"] + np.array([0.0, 0.0, -0.25]), real_pos=scene["start"])
+        cfg = pl.launch_config()
+        for k, v in (expect or {}).items():
+            assert cfg[k] == v, (k, cfg)
+        agents = _sample(int(scene["n_agents"]), n_sample)
+        obs = scene["obstacles"].copy()
+        for _ in range(n_ticks):
+            sh.shadow_tick(pl, scene, obs, ip, A, st, agents=agents)
+            if dynamic:
+                obs = scenes.advance_live_obstacles(obs)
+    finally:
+        pl.close()
+    return st
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_rollout_w64, one obstacle slot per lane (M <= 60)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("policy", ["xact", "ieee", "fast", "fma"])
+def test_w64_one_slot(pmaf, scenes, policy):
+    st = run_ticks(pmaf, scenes, scenes.static1_scene(16, 1), 20, policy, "w64 one-slot C1",
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1, priority_slices=False))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fast", "fma"])
+def test_w64_one_slot_dynamic(pmaf, scenes, policy):
+    st = run_ticks(pmaf, scenes, scenes.dyn1_scene(10, 1), 20, policy, "w64 one-slot dyn1", dynamic=True,
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+def test_w64_one_slot_lds_sum(pmaf, scenes, monkeypatch):
+    monkeypatch.setenv("PMAF_SUM", "lds")
+    st = run_ticks(pmaf, scenes, scenes.dyn1_scene(10, 1), 20, "xact", "w64 one-slot LDS sum", dynamic=True,
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fma"])
+def test_w64_k_step(pmaf, scenes, policy):
+    st = run_ticks(pmaf, scenes, scenes.static1_scene(16, 20), 2, policy, "w64 C1 20-step",
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1))
+    st.assert_ok(K_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fast"])
+def test_w64_general_step(pmaf, scenes, monkeypatch, policy):
+    """PMAF_PLAIN_STEP=0: the general step, with a non-unit mass and agents without attraction"""
+    monkeypatch.setenv("PMAF_PLAIN_STEP", "0")
+    sc = scenes.dyn1_scene(10, 6)
+    sc["agent_mass"] = 1.5
+    sc["k_attr"] = np.array([4.0, 0.0, 4.0, 4.0, 0.0, 4.0, 3.0, 0.0, 4.0, 5.0])
+    st = run_ticks(pmaf, scenes, sc, 6, policy, "w64 general step", dynamic=True,
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1))
+    st.assert_ok(K_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("policy,m", [("xact", 62), ("fma", 64), ("xact", 200), ("fma", 128)])
+def test_w64_tiles(pmaf, scenes, monkeypatch, policy, m):
+    """2-4 obstacle tiles per lane of the one-wave kernel (PMAF_MW=0 keeps it for M = 61..256)"""
+    monkeypatch.setenv("PMAF_MW", "0")
+    sc = scenes.synthetic_scene(16, 1, m, 7, m, dynamic=True)
+    st = run_ticks(pmaf, scenes, sc, 4, policy, "w64 tiles M=%d" % m, dynamic=True, n_sample=8,
+                   expect=dict(lanes_per_agent=64, waves_per_agent=1))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+def test_w64_sliced(pmaf, scenes):
+    """k_rollout_w64_sliced: one-slot rollouts between one and two waves per SIMD of this device"""
+    simds = _simds()
+    for policy in ("xact", "fma"):
+        sc = scenes.synthetic_scene(simds + simds // 2, 1, 24, 8, 1, dynamic=True)
+        st = run_ticks(pmaf, scenes, sc, 3, policy, "w64 sliced", dynamic=True, lpa=64, n_sample=16,
+                       expect=dict(lanes_per_agent=64, waves_per_agent=1, priority_slices=True))
+        st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_rollout_mw, k_rollout_grp, generic k_rollout
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("waves", [2, 3, 4])
+@pytest.mark.parametrize("policy", ["xact", "fast", "fma"])
+def test_mw(pmaf, scenes, monkeypatch, waves, policy):
+    monkeypatch.setenv("PMAF_MW", str(waves))
+    sc = scenes.synthetic_scene(14, 1, 100, 7, 100, dynamic=True)
+    st = run_ticks(pmaf, scenes, sc, 3, policy, "mw W=%d" % waves, dynamic=True, n_sample=6,
+                   expect=dict(waves_per_agent=waves))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("lpa", [8, 16, 32])
+@pytest.mark.parametrize("policy", ["xact", "fma"])
+def test_grp(pmaf, scenes, lpa, policy):
+    sc = scenes.synthetic_scene(64, 1, 32, 2, 0, dynamic=True)
+    st = run_ticks(pmaf, scenes, sc, 4, policy, "grp LPA %d" % lpa, lpa=lpa, dynamic=True, n_sample=12,
+                   expect=dict(lanes_per_agent=lpa))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+def test_grp_k_step(pmaf, scenes):
+    sc = scenes.synthetic_scene(64, 12, 32, 2, 0, dynamic=True)
+    st = run_ticks(pmaf, scenes, sc, 2, "xact", "grp LPA 16 12-step", lpa=16, dynamic=True, n_sample=8,
+                   expect=dict(lanes_per_agent=16))
+    st.assert_ok(K_STEP_MAX_UNDECIDABLE)
+
+
+@pytest.mark.parametrize("lpa", [64, 16, 8])
+def test_generic(pmaf, scenes, monkeypatch, lpa):
+    monkeypatch.setenv("PMAF_FORCE_GENERIC", "1")
+    st = run_ticks(pmaf, scenes, scenes.dyn1_scene(10, 1), 10, "xact", "generic LPA %d" % lpa, lpa=lpa, dynamic=True,
+                   expect=dict(lanes_per_agent=lpa))
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_plan_steps, k_link_force, k_eval_obstacle_distance, exact ties
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lpa", [0, 16, 1])
+def test_stepping_api(pmaf, scenes, lpa):
+    A = hp.Arith("xact")
+    st = sh.Stats("stepping API LPA %d" % lpa)
+    sc = scenes.synthetic_scene(8, 40, 16, config_id=2, dynamic=True)
+    pl = _planner(pmaf, sc, "xact", lpa)
+    try:
+        ip = sh.start(pl, sc)
+        pl.set_agent_pos_and_vels(np.array([-0.2, 0.05, 0.68]), np.array([0.15, -0.01, 0.02]))
+        sh.shadow_steps(pl, sc, sc["obstacles"], ip, A, st, 15)
+    finally:
+        pl.close()
+    st.assert_ok(ONE_STEP_MAX_UNDECIDABLE)
+
+
+def test_link_force_and_eval_obstacle_distance(pmaf, scenes):
+    A = hp.Arith("xact")
+    st = sh.Stats("link_force / eval_obstacle_distance")
+    sc = scenes.static1_scene(16, 4)
+    obs = sc["obstacles"].copy()
+    obs[-1, :3] = [0.1, 0.05, 0.8]
+    rng = np.random.default_rng(5)
+    lp = obs[-1, :3] + rng.uniform(-0.4, 0.4, (48, 3))
+    lp[0] = obs[-1, :3]
+    lp[1] = obs[-1, :3] + [0.0, 0.0, 0.5]
+    lp[2] = obs[-1, :3] + [0.0, 0.0, 0.15]
+    kr = rng.uniform(0.01, 0.1, 48)
+    pl = _planner(pmaf, sc, "xact")
+    try:
+        sh.start(pl, sc)
+        sh.shadow_link_force(pl, sc, lp, kr, obs, A, st)
+        for p in lp[::6]:
+            pl.set_agent_positions(p)
+            sh.shadow_eval_obstacle_distance(pl, sc, obs, A, st)
+    finally:
+        pl.close()
+    st.assert_ok(0.02)
+
+
+@pytest.mark.parametrize("kernel", ["default", "grp16", "generic"])
+def test_exact_tie_scenes(pmaf, monkeypatch, kernel):
+    """each tie decided with bound 0 by the reference; the kernel takes the same side"""
+    lpa = 16 if kernel == "grp16" else 0
+    if kernel == "generic":
+        monkeypatch.setenv("PMAF_FORCE_GENERIC", "1")
+        lpa = 64
+    A = hp.Arith("xact")
+    st = sh.Stats("exact-tie scenes, %s" % kernel)
+    for edge in hp_edges.EDGES:
+        edge.run(lambda sc: _planner(pmaf, sc, "xact", lpa), A, st)
+    st.assert_ok(0.0)
