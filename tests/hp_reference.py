@@ -478,6 +478,7 @@ def update_position_and_velocity(A, a, force, dt):
     if A.decide("vel_clamp", vn, ">", a.vel_max):
         vel = A.vscale(A.div(a.vel_max, vn), vel)
     a.vel = vel
+    a.acc = acc
     a.path.append(new_pos)
 
 

@@ -2,9 +2,11 @@
 time, on the planner's OWN fp64 state read back through its getters: every comparison starts from exact inputs, so an
 error never compounds across ticks and no chaotic amplification comes into play.
 
-The planner is anything with the CfManager surface of oracle/orc.py:OraclePlanner and the package's PmafPlanner
-(one population). Passing rule: |planner - reference| <= BOUND_FACTOR * bound on every compared component, and the
-planner takes the reference's side of every branch the reference decides.
+The planner is anything with the CfManager surface of oracle/orc.py:OraclePlanner and the package's PmafPlanner:
+one population, or P populations (attribute P > 1; every getter then returns a [P, ...] array, best() the per-population
+types and ids). Multi-population calls take the list of P scene dicts, obstacle rows [P, M, 7] and init_pos [P, 3].
+Passing rule: |planner - reference| <= BOUND_FACTOR * bound on every compared component, and the planner takes the
+reference's side of every branch the reference decides.
 """
 import numpy as np
 
@@ -29,6 +31,7 @@ class Stats:
         self.components = 0
         self.seen = {}
         self.failures = []
+        self.notes = []           # callables returning extra report lines (tests/hp_anchored.py)
 
     def merge_seen(self, seen):
         for k, v in seen.items():
@@ -78,6 +81,7 @@ class Stats:
             self.worst_at)]
         lines.append("    branches: " + " ".join("%s:%s" % (b, "".join(sorted("TF"[not o] for o in self.seen.get(b, ()))) or "-")
                                            for b in hp.BRANCHES))
+        lines += [f() for f in self.notes]
         return "\n".join(lines)
 
     def assert_ok(self, max_undecidable=0.05, min_compared=1):
@@ -116,16 +120,29 @@ def start(planner, scene, init_pos=None, real_pos=None):
     return np.asarray(init_pos, dtype=np.float64)
 
 
-def snapshot(planner):
-    """every getter the shadowing reads, as numpy arrays (one population)"""
+def n_populations(planner):
+    return int(getattr(planner, "P", 1))
+
+
+def snapshot(planner, pop=None):
+    """every getter the shadowing reads, as numpy arrays: one population; for a P-population planner population `pop`,
+    or (pop=None) the list of every population's"""
+    P = n_populations(planner)
     s = {}
     s["real_pos"], s["real_vel"], _ = [np.array(x) for x in planner.real_state()]
     s["real_known"], s["real_rot"] = [np.array(x) for x in planner.real_known()]
     s["paths"], s["n"] = [np.array(x) for x in planner.paths()]
     for k in ("agent_vel", "min_obs_dist", "rot_vecs", "known", "success", "costs"):
         s[k] = np.array(getattr(planner, k)())
-    s["best_id"], s["best_type"] = planner.best_id(), planner.best_type()
-    return s
+    if P == 1:
+        s["best_id"], s["best_type"] = planner.best_id(), planner.best_type()
+        return s
+    types, ids = [np.array(x) for x in planner.best()]
+    s["best_id"], s["best_type"] = ids, types
+    per = [{k: v[p] for k, v in s.items()} for p in range(P)]
+    for q in per:
+        q["best_id"], q["best_type"] = int(q["best_id"]), int(q["best_type"])
+    return per if pop is None else per[pop]
 
 
 def check_evaluate(A, st, scene, pre, costs, best, agents):
@@ -193,21 +210,63 @@ def check_rollouts(A, st, scene, pos, vel, known, pre_rot, pre_success, post, ob
         st.run(A, roll)
 
 
-def shadow_tick(planner, scene, obs_rows, init_pos, A, st, agents=None):
+def coupled_rows(obs_rows, pre, coupling):
+    """the obstacle rows a population of a coupled handle actually sees this tick: for each coupled population p
+    (coupling {p: (src_pop, radius)}), the trailing row is the source population's previous real position, velocity 0,
+    the coupling radius (shard.DualArmCoupling, include/pmaf.h "peer mailboxes")"""
+    out = np.array(obs_rows, dtype=np.float64, copy=True)
+    for p, (src, radius) in (coupling or {}).items():
+        out[p, -1, 0:3] = pre[src]["real_pos"]
+        out[p, -1, 3:6] = 0.0
+        out[p, -1, 6] = radius
+    return out
+
+
+def shadow_tick(planner, scene, obs_rows, init_pos, A, st, agents=None, rollouts=None, coupling=None):
     """one planCallback tick (evaluate, move the real agent, reset, roll out; B/src/panda_bimanual_control.cpp:336-352)
     shadowed: costs from the previous paths, the real agent's step from the previous real state with the agent selected
-    this tick, every sampled agent's rollout from the new real state"""
-    agents = list(range(int(scene["n_agents"]))) if agents is None else list(agents)
-    obs_rows = np.asarray(obs_rows, dtype=np.float64)
+    this tick, every sampled agent's rollout from the new real state. rollouts: the rollout checker (check_rollouts, or
+    tests/hp_anchored.py's walker). scene a list of P scene dicts: a P-population planner, every population shadowed
+    (obs_rows [P, M, 7], init_pos [P, 3], coupling as in coupled_rows); returns the per-population best indices."""
+    rollouts = check_rollouts if rollouts is None else rollouts
+    if isinstance(scene, dict):
+        agents = list(range(int(scene["n_agents"]))) if agents is None else list(agents)
+        obs_rows = np.asarray(obs_rows, dtype=np.float64)
+        pre = snapshot(planner)
+        best = int(planner.tick(obs_rows, scene["dt"], scene["cost_gains"], scene["ws_limits"]))
+        post = snapshot(planner)
+        assert post["best_id"] == best + 1
+        check_evaluate(A, st, scene, pre, post["costs"], best, agents)
+        check_real(A, st, scene, pre, post, init_pos, obs_rows, best)
+        rollouts(A, st, scene, post["real_pos"], post["real_vel"], post["real_known"], pre["rot_vecs"],
+                 pre["success"], post, obs_rows, init_pos, agents)
+        return best
+    scs = list(scene)
+    P = len(scs)
+    assert n_populations(planner) == P
+    obs_rows = np.asarray(obs_rows, dtype=np.float64).reshape(P, -1, 7)
+    init_pos = np.asarray(init_pos, dtype=np.float64).reshape(P, 3)
     pre = snapshot(planner)
-    best = int(planner.tick(obs_rows, scene["dt"], scene["cost_gains"], scene["ws_limits"]))
+    s0 = scs[0]
+    best = [int(b) for b in np.ravel(planner.tick(obs_rows, s0["dt"], s0["cost_gains"], s0["ws_limits"]))]
     post = snapshot(planner)
-    assert post["best_id"] == best + 1
-    check_evaluate(A, st, scene, pre, post["costs"], best, agents)
-    check_real(A, st, scene, pre, post, init_pos, obs_rows, best)
-    check_rollouts(A, st, scene, post["real_pos"], post["real_vel"], post["real_known"], pre["rot_vecs"],
-                   pre["success"], post, obs_rows, init_pos, agents)
+    rows = coupled_rows(obs_rows, pre, coupling)
+    for p, sc in enumerate(scs):
+        ag = list(range(int(sc["n_agents"]))) if agents is None else list(agents)
+        assert post[p]["best_id"] == best[p] + 1, (p, post[p]["best_id"], best[p])
+        check_evaluate(A, st, sc, pre[p], post[p]["costs"], best[p], ag)
+        check_real(A, st, sc, pre[p], post[p], init_pos[p], rows[p], best[p])
+        _call_rollouts(rollouts, A, st, sc, pre[p], post[p], rows[p], init_pos[p], ag, "pop %d " % p)
     return best
+
+
+def _call_rollouts(rollouts, A, st, sc, pre, post, rows, init_pos, agents, label):
+    args = (A, st, sc, post["real_pos"], post["real_vel"], post["real_known"], pre["rot_vecs"], pre["success"], post,
+            rows, init_pos, agents)
+    if rollouts is check_rollouts:
+        rollouts(*args)
+    else:
+        rollouts(*args, label=label)
 
 
 def shadow_reset_rollout(planner, scene, pos, vel, obs_rows, init_pos, A, st, agents=None):

@@ -6,11 +6,15 @@ evaluation order with it and carries a rounding-error bound (tests/hp_shadow.py)
 exact-tie scenes (tests/hp_edges.py) and the module's independence. Run with -s to see the per-case report.
 """
 import ast
+import json
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
+import hp_anchored as ha
 import hp_edges
 import hp_reference as hp
 import hp_shadow as sh
@@ -238,3 +242,341 @@ def test_reference_is_independent_of_the_oracle_and_the_package():
     assert mods <= {"math", "itertools", "mpmath.ctx_mp"}, mods
     for bad in ("oracle", "orc", "ctypes", "pmaf", "torch", "numpy"):
         assert not any(m == bad or m.startswith(bad + ".") for m in mods), bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# anchored walks: every step of full-length rollouts (tests/hp_anchored.py)
+# ---------------------------------------------------------------------------------------------------------------------
+ANCHORED_MAX_UNDECIDABLE = 0.02
+
+
+def _task_scene(scenes, name):
+    recs = json.load(open(os.path.join(HERE, "golden", "task_scenes.json")))
+    return scenes.scene_from_record(recs[name], name)
+
+
+def _anchored_ticks(orc, scenes, scene, n_ticks, name, agents, frac, dynamic=False, walk_from=0, policy="xact"):
+    """n_ticks planCallback ticks of the oracle; from tick walk_from on every sampled agent's rollout is walked"""
+    A = hp.Arith(policy)
+    st = sh.Stats(name)
+    pl = orc.OraclePlanner(scene, mgr_init_pos=scene["start"])
+    try:
+        ip = sh.start(pl, scene, init_pos=scene["start"] + np.array([0.0, 0.0, -0.25]), real_pos=scene["start"])
+        obs = scene["obstacles"].copy()
+        for t in range(n_ticks):
+            sh.shadow_tick(pl, scene, obs, ip, A, st, agents=agents if t >= walk_from else [],
+                           rollouts=ha.walker(frac, seed=t))
+            if dynamic:
+                obs = scenes.advance_live_obstacles(obs)
+    finally:
+        pl.close()
+    return st
+
+
+class PopOracles:
+    """P oracle planners presented as one P-population planner (the [P, ...] getters of PmafPlanner). coupling
+    {p: (src_pop, radius)} replaces population p's trailing obstacle by population src_pop's previous real position,
+    velocity 0 (include/pmaf.h "peer mailboxes"), as the device-side coupling does"""
+
+    def __init__(self, orc, scs, coupling=None):
+        self.P = len(scs)
+        self.pl = [orc.OraclePlanner(s, mgr_init_pos=s["start"]) for s in scs]
+        self.coupling = coupling or {}
+
+    def close(self):
+        for q in self.pl:
+            q.close()
+
+    def _each(self, name, *args):
+        return [getattr(q, name)(*args) for q in self.pl]
+
+    def set_initial_position(self, pos):
+        for q, x in zip(self.pl, np.reshape(pos, (self.P, 3))):
+            q.set_initial_position(x)
+
+    def set_real_position(self, pos):
+        for q, x in zip(self.pl, np.reshape(pos, (self.P, 3))):
+            q.set_real_position(x)
+
+    def tick(self, obstacles, dt, cost_gains, ws):
+        obs = np.array(obstacles, dtype=np.float64).reshape(self.P, -1, 7)
+        prev = [q.real_state()[0] for q in self.pl]
+        for p, (src, radius) in self.coupling.items():
+            obs[p, -1] = list(prev[src]) + [0.0, 0.0, 0.0, radius]
+        return np.array([q.tick(obs[p], dt, cost_gains, ws) for p, q in enumerate(self.pl)])
+
+    def real_state(self):
+        return [np.stack(x) for x in zip(*self._each("real_state"))]
+
+    def real_known(self):
+        return [np.stack(x) for x in zip(*self._each("real_known"))]
+
+    def paths(self):
+        return [np.stack(x) for x in zip(*self._each("paths"))]
+
+    def best(self):
+        return np.array(self._each("best_type")), np.array(self._each("best_id"))
+
+
+for _m in ("agent_vel", "min_obs_dist", "rot_vecs", "known", "success", "costs"):
+    setattr(PopOracles, _m, (lambda m: lambda self: np.stack(self._each(m)))(_m))
+
+
+def _pop_case(orc, scenes, name, coupling=None, swap_goals=False, n_ticks=3):
+    """C4-shaped: two arms, each arm's trailing obstacle the other arm's end effector. coupling None: coupled on the
+    host (shard.DualArmCoupling builds the rows the planner and the shadow both get); otherwise coupled inside the
+    planner and rebuilt by the shadow (hp_shadow.coupled_rows)"""
+    arms = scenes.dual_arm_scenes(16, 150, 12)
+    starts = np.stack([s["start"] for s in arms])
+    made = [dict(s) for s in arms]
+    if swap_goals:                                   # a planner that mixes up the per-population goal
+        made[0]["goal"], made[1]["goal"] = arms[1]["goal"], arms[0]["goal"]
+    A = hp.Arith("xact")
+    st = sh.Stats(name)
+    pl = PopOracles(orc, made, coupling)
+    try:
+        pl.set_initial_position(starts)
+        obs = np.stack([s["obstacles"] for s in arms])
+        host = None if coupling else graft.load_package().shard.DualArmCoupling(obs, 0.1)
+        for t in range(n_ticks):
+            rows = host.coupled_obstacles(pl.real_state()[0]) if host else obs
+            sh.shadow_tick(pl, arms, rows, starts, A, st, agents=[0, 5], rollouts=ha.walker(0.5, seed=t),
+                           coupling=coupling)
+    finally:
+        pl.close()
+    return st
+
+
+def case_anchored_c2(orc, scenes):
+    return _anchored_ticks(orc, scenes, scenes.config_scene("C2"), 1, "anchored C2", list(range(0, 64, 8)), 0.5)
+
+
+def case_anchored_c5_scene1(orc, scenes):
+    sc = scenes.config_scene("C5", scene_id=1, dynamic=True)
+    return _anchored_ticks(orc, scenes, sc, 3, "anchored C5 scene 1 dyn", [3, 7, 500, 1001], 0.25, dynamic=True)
+
+
+def case_anchored_c3(orc, scenes):
+    return _anchored_ticks(orc, scenes, scenes.config_scene("C3"), 1, "anchored C3", [17], 0.1)
+
+
+def case_anchored_kobo1(orc, scenes):
+    sc = _task_scene(scenes, "sim_kobo_dyn_spheres1")
+    return _anchored_ticks(orc, scenes, sc, 2, "anchored sim_kobo_dyn_spheres1", [4], 0.1, dynamic=True, walk_from=1)
+
+
+def case_anchored_pop_host(orc, scenes):
+    return _pop_case(orc, scenes, "anchored C4-shaped, P = 2, coupled on the host")
+
+
+def case_anchored_pop_mailbox(orc, scenes):
+    return _pop_case(orc, scenes, "anchored C4-shaped, P = 2, coupled in the planner", coupling={0: (1, 0.1), 1: (0, 0.1)})
+
+
+ANCHORED = {
+    "anchored_c2": case_anchored_c2,
+    "anchored_c5_scene1": case_anchored_c5_scene1,
+    "anchored_c3": case_anchored_c3,
+    "anchored_kobo1": case_anchored_kobo1,
+    "anchored_pop_host": case_anchored_pop_host,
+    "anchored_pop_mailbox": case_anchored_pop_mailbox,
+}
+CASES.update(ANCHORED)
+
+
+@pytest.mark.parametrize("name", list(ANCHORED))
+def test_oracle_anchored_rollouts(orc, scenes, name):
+    """every step of full-length rollouts (200-1500 steps) within the reference's bound from the oracle's own state at
+    that step; the guard, success, min_obs_dist, known flags, latched rotation vectors and final velocity"""
+    st = _run_case(name, orc, scenes)
+    assert st.walk.horizon >= 150, st.report()
+    st.assert_ok(max_undecidable=ANCHORED_MAX_UNDECIDABLE, min_compared=10)
+
+
+# -- teeth: planners that are wrong in small ways must fail -----------------------------------------------------------
+def _tick_then(orc, scene, n_ticks, dynamic, scenes):
+    """an oracle after n_ticks ticks, with its rollout's inputs and outputs"""
+    pl = orc.OraclePlanner(scene, mgr_init_pos=scene["start"])
+    ip = sh.start(pl, scene, init_pos=scene["start"] + np.array([0.0, 0.0, -0.25]), real_pos=scene["start"])
+    obs = scene["obstacles"].copy()
+    for t in range(n_ticks):
+        pre = sh.snapshot(pl)
+        pl.tick(obs, scene["dt"], scene["cost_gains"], scene["ws_limits"])
+        rows = obs
+        if dynamic:
+            obs = scenes.advance_live_obstacles(obs)
+    return pl, ip, pre, sh.snapshot(pl), rows
+
+
+def _walk(scene, ip, pre, post, rows, i, frac=1.0, policy="xact"):
+    A = hp.Arith(policy)
+    st = sh.Stats("mutant")
+    ha.walk_agent(A, st, scene, i, post["real_pos"], post["real_vel"], post["real_known"], pre["rot_vecs"][i],
+                  pre["success"], post, rows, ip, frac=frac)
+    print(st.report())
+    return st
+
+
+def _fails_with(st, what):
+    assert st.failures, "the mutant passed:\n" + st.report()
+    assert any(what in f for f in st.failures), "failed, but not for %r: %s" % (what, st.failures[:4])
+
+
+@pytest.fixture(scope="module")
+def c2_tick(orc, scenes):
+    sc = scenes.config_scene("C2")
+    pl, ip, pre, post, rows = _tick_then(orc, sc, 1, False, scenes)
+    pl.close()
+    return sc, ip, pre, post, rows
+
+
+def test_mutant_interior_point_256_ulp(orc, scenes):
+    """one interior path point (step 150) moved by 256 ulp. The walk's resolution there is set by the velocity ball: after
+    150 steps its radius (the sum of every step's position rounding, 2 |dp| / dt each) is ~6e-12 m/s, and even the
+    second-difference check, from which the radius drops out, carries the force's sensitivity to it -- ~1e-14 m, about
+    100 ulp, on this free-space stretch of sim_kobo_dyn_spheres1 (~1e-13 m near C2's spheres). 64 ulp is below that."""
+    sc = _task_scene(scenes, "sim_kobo_dyn_spheres1")
+    sc["max_prediction_steps"] = 201
+    pl, ip, pre, post, rows = _tick_then(orc, sc, 1, True, scenes)
+    pl.close()
+    i = 3
+    assert post["n"][i] > 180
+    ok = _walk(sc, ip, pre, post, rows, i)
+    assert not ok.failures and ok.undecidable == 0, ok.report()
+    post = dict(post, paths=post["paths"].copy())
+    c = int(np.argmax(np.abs(post["paths"][i, 150])))
+    x = post["paths"][i, 150, c]
+    post["paths"][i, 150, c] = x + 256 * np.spacing(x)
+    _fails_with(_walk(sc, ip, pre, post, rows, i), "path[150]")
+
+
+def test_mutant_last_steps_longer_dt(c2_tick):
+    """a path whose last 10 steps were integrated with dt (1 + 1e-9): each of their increments scaled by 1 + 1e-9"""
+    sc, ip, pre, post, rows = c2_tick
+    i = 16
+    n = int(post["n"][i])
+    post = dict(post, paths=post["paths"].copy())
+    p = post["paths"][i]
+    orig = p[:n].copy()
+    for k in range(n - 10, n):
+        p[k] = p[k - 1] + (orig[k] - orig[k - 1]) * (1.0 + 1e-9)
+    _fails_with(_walk(sc, ip, pre, post, rows, i, frac=0.0), "path[%d]" % (n - 1))
+
+
+@pytest.fixture(scope="module")
+def c5_tick(orc, scenes):
+    sc = scenes.config_scene("C5", scene_id=1, dynamic=True)
+    pl, ip, pre, post, rows = _tick_then(orc, sc, 3, True, scenes)
+    return sc, pl, ip, pre, post, rows
+
+
+def test_mutant_obstacles_advanced_before_the_step(orc, c5_tick):
+    """the rollout's private obstacles predicted BEFORE each step instead of after: the same oracle, reset with rows
+    advanced by one predictObstacles"""
+    sc, pl, ip, pre, post, rows = c5_tick
+    i = 7
+    adv = rows.copy()
+    adv[:, 0:3] = adv[:, 0:3] + sc["dt"] * adv[:, 3:6]
+    pl.reset_agents(post["real_pos"], post["real_vel"], adv)
+    pl.rollout()
+    bad = sh.snapshot(pl)
+    _fails_with(_walk(sc, ip, pre, bad, rows, i, frac=0.1), "path[")
+
+
+def test_mutant_latch_one_step_late(c5_tick):
+    """a latch one step late: the latched rotation vector the planner reports is the one of the next path point"""
+    sc, pl, ip, pre, post, rows = c5_tick
+    for i in (3, 7, 500):
+        st = _walk(sc, ip, pre, post, rows, i, frac=0.0)
+        assert not st.failures, st.report()
+        if st.walk.latches:
+            break
+    _, k, j = st.walk.latches[0]
+    A = hp.Arith("xact")
+    own = hp.obstacles_from_rows(A, rows, radii=sc["obstacles"][:, 6])
+    for _ in range(k + 1):
+        hp.predict_obstacles(A, own, sc["dt"])
+    late = hp.rotation_vector(A, sh.agent_types(sc)[i], A.v3(post["paths"][i, k + 1]), A.v3(sc["goal"]), own, j,
+                              [A.v3(r) for r in sc["random_vecs"][i]])
+    bad = dict(post, rot_vecs=post["rot_vecs"].copy())
+    bad["rot_vecs"][i, j] = [q.f for q in late]
+    _fails_with(_walk(sc, ip, pre, bad, rows, i, frac=0.0), "rot[%d] latched at step %d" % (j, k))
+
+
+def test_mutant_population_goals_swapped(orc, scenes):
+    """a two-population planner that gives each population the other's goal"""
+    st = _pop_case(orc, scenes, "mutant: goals swapped", swap_goals=True, n_ticks=1)
+    print(st.report())
+    assert st.failures, st.report()
+    assert any("path[" in f or "real pos" in f for f in st.failures), st.failures[:4]
+
+
+# -- the ball itself ---------------------------------------------------------------------------------------------------
+def _fma(a, b, c):
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _update(p, v, a, dt, vmax, form):
+    """updatePositionAndVelocity in fp64, one of the operation sequences the policies may use"""
+    half = ((0.5 * a) * dt) * dt
+    if form == "left":
+        p1 = (p + half) + v * dt
+    elif form == "right":
+        p1 = p + (half + v * dt)
+    else:                                        # fma(dt, v, p) + half, and fma(dt, a, v)
+        p1 = np.array([_fma(dt, v[k], p[k]) for k in range(3)]) + half
+    u = np.array([_fma(dt, a[k], v[k]) for k in range(3)]) if form == "fma" else v + a * dt
+    un = np.sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2])
+    if un > vmax:
+        u = u * (vmax / un)
+    return p1, u
+
+
+@pytest.mark.parametrize("policy,form", [("xact", "left"), ("xact", "right"), ("fma", "fma"), ("fast", "left")])
+def test_ball_contains_fp64_velocity(policy, form):
+    """for random positions, velocities in a ball, accelerations |a| <= 13 and both clamp outcomes, the ball that
+    hp_anchored derives from the two fp64 positions contains the fp64 velocity, under the operation sequence given"""
+    A = hp.Arith(policy)
+    rng = np.random.default_rng(23)
+    worst, n, clamped = 0.0, 0, set()
+    for t in range(300):
+        dt = [0.01, 0.02, 0.0625][t % 3]
+        vmax = rng.uniform(0.1, 0.6)
+        p = rng.uniform(-1.0, 1.0, 3)
+        c = rng.normal(size=3)
+        c *= vmax * rng.uniform(0.3, 1.0) / np.linalg.norm(c)
+        r = [0.0, 1e-13, 1e-11][t % 3]
+        d = rng.normal(size=3)
+        v = c + d * (r * rng.uniform(0, 1) / np.linalg.norm(d))
+        a = rng.normal(size=3)
+        a *= rng.uniform(0, 13.0) / np.linalg.norm(a)
+        if t % 5 == 0:
+            a *= 13.0 / np.linalg.norm(a)
+        p1, v1 = _update(p, v, a, dt, vmax, form)
+        ball = ha.Ball([hp.MPF(float(x)) for x in c], r)
+        try:
+            nb = ball.advance(A, p, p1, dt, vmax)
+        except hp.Undecidable:
+            continue
+        clamped.update(A.seen.get("vel_clamp", ()))
+        q = nb.ratio(v1)
+        assert q <= 1.0, (t, q, nb.r)
+        worst, n = max(worst, q), n + 1
+    print("%s / %s: %d samples, worst |v - c| / r = %.3g" % (policy, form, n, worst))
+    assert n >= 250 and clamped == {True, False}
+
+
+def test_new_shadow_modules_are_independent_of_the_oracle_and_the_package():
+    """hp_anchored.py and hp_shadow.py read planners only through the object handed to them: no import of oracle/, the
+    package, ctypes or torch"""
+    for name in ("hp_anchored.py", "hp_shadow.py"):
+        tree = ast.parse(open(os.path.join(HERE, name)).read())
+        mods = set()
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                mods.update(a.name for a in node.names)
+            elif isinstance(node, ast.ImportFrom):
+                mods.add(node.module or "")
+            elif isinstance(node, ast.Call) and getattr(node.func, "id", getattr(node.func, "attr", "")) in ("__import__", "import_module"):
+                raise AssertionError("dynamic import in %s" % name)
+        assert mods <= {"math", "numpy", "hp_reference", "hp_shadow"}, (name, mods)

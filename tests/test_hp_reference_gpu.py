@@ -6,10 +6,14 @@ here each output is held to the reference's rounding-error bound for the policy'
 each decided branch to the reference's side. launch_config() confirms which kernel ran. Large shapes compare a seeded
 sample of agents (the agents of a rollout are independent). Run with -s to see the per-case report.
 """
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
+import hp_anchored as ha
 import hp_edges
 import hp_reference as hp
 import hp_shadow as sh
@@ -209,3 +213,120 @@ def test_exact_tie_scenes(pmaf, monkeypatch, kernel):
     for edge in hp_edges.EDGES:
         edge.run(lambda sc: _planner(pmaf, sc, "xact", lpa), A, st)
     st.assert_ok(0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# anchored walks: every step of full-length rollouts, every population (tests/hp_anchored.py)
+# ---------------------------------------------------------------------------------------------------------------------
+ANCHORED_MAX_UNDECIDABLE = 0.02
+
+
+def _anchored(pmaf, scenes, scs, n_ticks, policy, name, agents, frac, lpa=0, expect=None, dynamic=False, walk_from=0,
+              host_coupling=False, mailbox=False):
+    """n_ticks ticks of one handle holding the populations `scs`; from tick walk_from on, the sampled agents of every
+    population are walked. host_coupling: C4 coupled on the host (shard.DualArmCoupling rows); mailbox: coupled inside the
+    handle through its peer mailbox, the shadow rebuilding the trailing rows"""
+    A = hp.Arith(policy)
+    st = sh.Stats("%s [%s]" % (name, policy))
+    single = len(scs) == 1
+    starts = np.stack([s["start"] for s in scs])
+    pl = pmaf.PmafPlanner(scs[0] if single else scs, device=0, mgr_init_pos=starts[0] if single else starts,
+                          lanes_per_agent=lpa, **POLICY_KW[policy])
+    try:
+        if single:
+            ip = sh.start(pl, scs[0], init_pos=starts[0] + np.array([0.0, 0.0, -0.25]), real_pos=starts[0])
+        else:
+            pl.set_initial_position(starts)
+            ip = starts
+        cfg = pl.launch_config()
+        for k, v in (expect or {}).items():
+            assert (cfg[k] >= 2) if v == ">=2" else (cfg[k] == v), (k, cfg)
+        coupling = None
+        if mailbox:
+            pmaf.shard.connect_peers(pl, None, 1, 0)
+            pmaf.shard.couple_dual_arm_on_device(pl, 1, 0, starts)
+            coupling = {0: (1, 0.1), 1: (0, 0.1)}
+        obs = np.stack([s["obstacles"] for s in scs])
+        host = pmaf.shard.DualArmCoupling(obs, 0.1) if host_coupling else None
+        for t in range(n_ticks):
+            rows = host.coupled_obstacles(pl.real_state()[0]) if host else obs
+            ag = agents(pl) if callable(agents) else agents
+            sh.shadow_tick(pl, scs[0] if single else scs, rows[0] if single else rows, ip, A, st,
+                           agents=ag if t >= walk_from else [], rollouts=ha.walker(frac, seed=t), coupling=coupling)
+            if dynamic:
+                obs = np.stack([scenes.advance_live_obstacles(o) for o in obs])
+        if mailbox:
+            pl.stop()
+            pl.peer_disconnect()
+    finally:
+        pl.close()
+    return st
+
+
+def _assert_anchored(st, min_horizon):
+    assert st.walk.horizon >= min_horizon, st.report()
+    st.assert_ok(ANCHORED_MAX_UNDECIDABLE, min_compared=4)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fma", "fast"])
+def test_anchored_c2_w64_one_slot(pmaf, scenes, policy):
+    """BASELINE C2 (the bench headline: 64 agents, H = 200, 32 spheres) on k_rollout_w64, one obstacle slot per lane"""
+    st = _anchored(pmaf, scenes, [scenes.config_scene("C2")], 3, policy, "anchored C2 w64 one-slot",
+                   _sample(64, 8), 0.15, expect=dict(lanes_per_agent=64, waves_per_agent=1, priority_slices=False))
+    _assert_anchored(st, 200)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fma"])
+def test_anchored_c3_mw(pmaf, scenes, policy):
+    """BASELINE C3 (256 agents, H = 500, 128 spheres) on k_rollout_mw at its default wave count"""
+    st = _anchored(pmaf, scenes, [scenes.config_scene("C3")], 1, policy, "anchored C3 mw", _sample(256, 4), 0.04,
+                   expect=dict(waves_per_agent=">=2"))
+    _assert_anchored(st, 400)
+
+
+@pytest.mark.parametrize("policy", ["xact", "fma"])
+def test_anchored_c5_grp(pmaf, scenes, policy):
+    """BASELINE C5 at full size: 8 populations x 1024 agents on k_rollout_grp, 16 lanes per agent; 2 agents of every
+    population (scene 1, the chaotic one, included)"""
+    scs = [scenes.config_scene("C5", scene_id=s) for s in range(8)]
+    st = _anchored(pmaf, scenes, scs, 2, policy, "anchored C5 8x1024 grp LPA 16", _sample(1024, 2, seed=11), 0.15,
+                   lpa=16, expect=dict(lanes_per_agent=16), walk_from=1)
+    _assert_anchored(st, 150)
+
+
+def test_anchored_c5x2_sliced(pmaf, scenes):
+    """two C5 scenes in one handle: k_rollout_w64_sliced (priority slices)"""
+    scs = [scenes.config_scene("C5", scene_id=s) for s in (0, 2)]
+    st = _anchored(pmaf, scenes, scs, 2, "fma", "anchored C5x2 w64 sliced", _sample(1024, 2, seed=12), 0.15,
+                   expect=dict(lanes_per_agent=64, priority_slices=True))
+    _assert_anchored(st, 150)
+
+
+def test_anchored_c4_host_coupling(pmaf, scenes):
+    """BASELINE C4: two arms, each arm's trailing obstacle the other arm's end effector, coupled on the host"""
+    st = _anchored(pmaf, scenes, scenes.dual_arm_scenes(), 3, "xact", "anchored C4 host coupling",
+                   _sample(256, 2, seed=13), 0.15, host_coupling=True)
+    _assert_anchored(st, 150)
+
+
+def test_anchored_c4_peer_mailbox(pmaf, scenes):
+    """BASELINE C4 coupled inside one handle through its peer mailbox: the shadow rebuilds each population's trailing
+    row from the other population's previous real position"""
+    st = _anchored(pmaf, scenes, scenes.dual_arm_scenes(), 3, "fma", "anchored C4 peer mailbox",
+                   _sample(256, 2, seed=13), 0.15, mailbox=True)
+    _assert_anchored(st, 150)
+
+
+@pytest.mark.parametrize("task", ["sim_kobo_dyn_spheres1", "sim_kobo_dyn_spheres2", "sim_kobo_dyn_spheres3"])
+def test_anchored_shipped_tasks(pmaf, scenes, task):
+    """the reference's shipped sim_kobo scenes (10 agents, H = 1500 / 1200, moving spheres): the agent selected last
+    tick and one more, sampled steps"""
+    recs = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "task_scenes.json")))
+    sc = scenes.scene_from_record(recs[task], task)
+
+    def best_plus_one(pl):
+        b = max(pl.best_id() - 1, 0)
+        return [b, (b + 5) % 10]
+    st = _anchored(pmaf, scenes, [sc], 2, "fma", "anchored %s" % task, best_plus_one, 0.08, dynamic=True,
+                   walk_from=1)
+    _assert_anchored(st, 500)            # a rollout that reaches the goal ends there (sim_kobo_dyn_spheres2: 915 steps)
