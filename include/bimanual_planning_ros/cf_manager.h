@@ -54,6 +54,14 @@ struct Vector6d {
 };
 #endif
 
+// result of CfManager::evaluatePaths: one entry per predicted agent (pmaf.h, "path audit")
+struct PathAudit {
+  std::vector<double> clearance;     // least surface distance of the path to any obstacle of the list [m]; < 0: penetration
+  std::vector<int> step;             // path point at which it is reached (-1: no comparable pair)
+  std::vector<int> obstacle;         // ... and the obstacle it is reached against
+  std::vector<int> first_violation;  // first path point with a clearance below the margin; the path's size if none
+};
+
 class CfManager {
   pmaf_planner *h_ = nullptr;
   int n_agents_ = 0;
@@ -417,6 +425,35 @@ class CfManager {
     int32_t best = 0;
     check(pmaf_evaluate(h_, gains, ws, &best), "evaluateAgents");
     return best;
+  }
+  // CfManager::evaluatePath: declared by the reference (cf_manager.h:130), never defined there; evaluateAgents ignores
+  // the list it is given (cf_manager.cpp:293-356) and scores the distances the rollout recorded against the obstacles
+  // of the previous reset. Here: the least clearance [m] of the SELECTED agent's current predicted path to the given
+  // list, every obstacle advanced with its velocity step by step (pmaf_evaluate_path); negative = penetration.
+  // std::runtime_error before the first evaluateAgents / planTick.
+  double evaluatePath(const std::vector<Obstacle> &obstacles) {
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("evaluatePath: obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    double c = 0.0;
+    check(pmaf_evaluate_path(h_, obs.data(), &c), "evaluatePath");
+    return c;
+  }
+  // ... and of every predicted agent's path, with the step and obstacle of the closest approach and the first step whose
+  // clearance falls below `margin` (pmaf_evaluate_paths; no reference equivalent)
+  PathAudit evaluatePaths(const std::vector<Obstacle> &obstacles, const double margin = 0.0) {
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("evaluatePaths: obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    PathAudit r;
+    r.clearance.resize(n_agents_);
+    std::vector<int32_t> st(n_agents_), ob(n_agents_), fv(n_agents_);
+    check(pmaf_evaluate_paths(h_, obs.data(), margin, r.clearance.data(), st.data(), ob.data(), fv.data(), nullptr),
+          "evaluatePaths");
+    r.step.assign(st.begin(), st.end());
+    r.obstacle.assign(ob.begin(), ob.end());
+    r.first_violation.assign(fv.begin(), fv.end());
+    return r;
   }
   // the whole planCallback sequence (B/src/panda_bimanual_control.cpp:336-352)
   // as one call: stop, evaluate, move the real agent one step, reset, start

@@ -271,6 +271,36 @@ int pmaf_set_agent_pos_and_vels(pmaf_planner *h, const double *pos, const double
  * its latest position against obstacles [P][n_obstacles][7]; out [P][N]. */
 int pmaf_eval_obstacle_distance(pmaf_planner *h, const double *obstacles, double *out);
 
+/* ---- path audit: the predicted paths against a LIVE obstacle list (exports added under ABI 7) ----
+ * The reference declares `double CfManager::evaluatePath(const std::vector<Obstacle> &obstacles)`
+ * (B/include/bimanual_planning_ros/cf_manager.h:130) and never defines it. CfManager::evaluateAgents takes the tick's
+ * fresh obstacle list and IGNORES it (B/src/cf_manager.cpp:293-356): its safety term is min_obs_dist_, recorded by the
+ * rollout against the obstacle copies of the previous reset -- field obstacles only, ungated steps only, floored at
+ * 1e-5 and capped at the shell radius (B/src/cf_agent.cpp:83-88). These two calls answer what that leaves open once the
+ * obstacles have moved: how close does each candidate path come to the list as it is NOW, to which obstacle, at which
+ * step, and from which step on is it no longer clear.
+ * For population p, agent a, the handle's CURRENT predicted paths x_0 .. x_{n-1} (n = n_points[p][a]; whatever wrote
+ * them: a rollout or the stepping calls) and EVERY obstacle j of obstacles [P][n_obstacles][7], the trailing repulsive
+ * one included:
+ *   o_j^0 = the given position, o_j^{k+1} = o_j^k + v_j * dt  per component, one multiply then one add, each rounded
+ *           (iterated like CfAgent::predictObstacles, B/src/cf_agent.cpp:270-276; dt = pmaf_params.dt)
+ *   c(k,j) = norm(x_k - o_j^k) - (radius + r_j)               (evalObstacleDistance, B/src/cf_agent.cpp:150-151;
+ *           norm = sqrt(dot) in the build's association, pmaf_eval_order; no floor, no cap: negative = penetration)
+ * clearance [P][N]       = min over (k,j) of c, found with a strict `<` from +infinity (a NaN pair never wins);
+ * step, obstacle [P][N]  = its argmin; ties go to the smallest k, then the smallest j; -1 when no pair won;
+ * first_violation [P][N] = the smallest k with c(k,j) < margin for some j, else n;
+ * per_obstacle [P][N][n_obstacles] = min over k of c(k,j).
+ * step / obstacle / first_violation / per_obstacle may each be NULL. An empty path gives +infinity, -1, -1, 0.
+ * Like the getters of rollout results the calls wait for the running rollout; they change no planner state (a tick
+ * sequence with audits in between is bit-identical to one without). The reference left the return value of
+ * evaluatePath open; here it is the clearance in metres. */
+int pmaf_evaluate_paths(pmaf_planner *h, const double *obstacles, double margin, double *clearance, int32_t *step,
+                        int32_t *obstacle, int32_t *first_violation, double *per_obstacle);
+/* CfManager::evaluatePath (declared at B/include/bimanual_planning_ros/cf_manager.h:130, undefined in the reference;
+ * evaluateAgents ignores its list, B/src/cf_manager.cpp:293-356): the clearance, as above, of the SELECTED agent's
+ * current path only; clearance [P]. PMAF_ERR_STATE before the first selection (pmaf_evaluate / pmaf_tick). */
+int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearance);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

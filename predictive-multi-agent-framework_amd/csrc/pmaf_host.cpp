@@ -194,6 +194,10 @@ struct pmaf_planner {
   double exchange_timeout_s = 60.0;    // PMAF_EXCHANGE_TIMEOUT_S: bound of the wait for a winner exchange
   double *d_link = nullptr, *h_link = nullptr;  // pmaf_link_force scratch (device / pinned host), grown on demand
   size_t link_scratch_doubles = 0;
+  // pmaf_evaluate_paths / pmaf_evaluate_path scratch, grown on demand: the obstacle track [P][cap][3][n_obs] and the
+  // outputs on the device, the outputs' pinned host mirror (one device-to-host copy per call)
+  char *d_audit = nullptr, *h_audit = nullptr;
+  size_t audit_bytes = 0;
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};
@@ -1055,6 +1059,8 @@ int pmaf_destroy(pmaf_planner *h) {
   if (h->h_np) (void)hipHostFree(h->h_np);
   if (h->d_link) (void)hipFree(h->d_link);
   if (h->h_link) (void)hipHostFree(h->h_link);
+  if (h->d_audit) (void)hipFree(h->d_audit);
+  if (h->h_audit) (void)hipHostFree(h->h_audit);
   for (auto &e : h->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto &e : h->ev_inflight) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   if (h->ev_mgr) (void)hipEventDestroy(h->ev_mgr);
@@ -1456,6 +1462,82 @@ int pmaf_eval_obstacle_distance(pmaf_planner *h, const double *obstacles, double
     pmaf_k_launch_eval_obstacle_distance(h->D, d_obs, h->d_plan_out, h->stream);
     HIP_CHECK(hipGetLastError());
     h->download(out, h->d_plan_out, (size_t)h->D.P * h->D.N);
+  });
+}
+
+// ---- path audit: the current predicted paths against a live obstacle list ----
+// The reference declares CfManager::evaluatePath(const std::vector<Obstacle> &) (B/include/bimanual_planning_ros/
+// cf_manager.h:130) without defining it, and evaluateAgents ignores its obstacle list (B/src/cf_manager.cpp:293-356).
+// One implementation behind both exports: only_best = the selected agent of every population (outputs [P]).
+static void evaluate_paths(pmaf_planner *h, const double *obstacles, double margin, bool only_best, double *clearance,
+                           int32_t *step, int32_t *obstacle, int32_t *first_violation, double *per_obstacle) {
+  const DevView &D = h->D;
+  const size_t n_obs = (size_t)D.n_obs, rows = only_best ? (size_t)D.P : (size_t)D.P * D.N;
+  check_range(obstacles, (size_t)D.P * n_obs * 7, "obstacles");
+  check_range(&margin, 1, "margin");
+  if ((size_t)D.cap * n_obs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "path audit: max_prediction_steps * n_obstacles must stay below 2^31");
+  h->use_device();
+  sync(h);   // behind the running rollout, like the getters of its results
+  // device scratch: track | clearance [rows] | per_obstacle [rows][n_obs] | step, obstacle, first_violation [rows] each
+  const size_t track_b = sizeof(double) * (size_t)D.P * D.cap * 3 * n_obs;
+  const size_t full = (size_t)D.P * D.N;   // (sized for the all-agents call: both exports share the buffer)
+  const size_t out_b = sizeof(double) * full + (per_obstacle ? sizeof(double) * full * n_obs : 0) + 3 * sizeof(int32_t) * full;
+  if (track_b + out_b > h->audit_bytes) {
+    if (h->d_audit) { (void)hipFree(h->d_audit); h->d_audit = nullptr; }
+    if (h->h_audit) { (void)hipHostFree(h->h_audit); h->h_audit = nullptr; }
+    h->audit_bytes = 0;
+    HIP_CHECK(hipMalloc((void **)&h->d_audit, track_b + out_b));
+    HIP_CHECK(hipHostMalloc((void **)&h->h_audit, out_b, hipHostMallocDefault));
+    h->audit_bytes = track_b + out_b;
+  }
+  char *d_out = h->d_audit + track_b;
+  AuditArgs A{};
+  A.obs = upload_plan_obstacles(h, obstacles);
+  A.track = reinterpret_cast<double *>(h->d_audit);
+  A.margin = margin;
+  A.only_best = only_best ? 1 : 0;
+  while ((1 << A.group_log2) < D.n_obs && A.group_log2 < 6) A.group_log2++;
+  size_t off = 0;
+  A.clearance = reinterpret_cast<double *>(d_out + off); off += sizeof(double) * rows;
+  if (per_obstacle) { A.per_obstacle = reinterpret_cast<double *>(d_out + off); off += sizeof(double) * rows * n_obs; }
+  A.step = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
+  A.obstacle = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
+  A.first_violation = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
+  pmaf_k_launch_path_audit(D, A, reinterpret_cast<double *>(h->d_audit), h->stream);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h->h_audit, d_out, off, hipMemcpyDeviceToHost, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  const char *src = h->h_audit;
+  std::memcpy(clearance, src, sizeof(double) * rows); src += sizeof(double) * rows;
+  if (per_obstacle) { std::memcpy(per_obstacle, src, sizeof(double) * rows * n_obs); src += sizeof(double) * rows * n_obs; }
+  int32_t *const outs[3] = {step, obstacle, first_violation};
+  for (int32_t *o : outs) {
+    if (o) std::memcpy(o, src, sizeof(int32_t) * rows);
+    src += sizeof(int32_t) * rows;
+  }
+}
+
+int pmaf_evaluate_paths(pmaf_planner *h, const double *obstacles, double margin, double *clearance, int32_t *step,
+                        int32_t *obstacle, int32_t *first_violation, double *per_obstacle) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_evaluate_paths: NULL argument");
+    evaluate_paths(h, obstacles, margin, false, clearance, step, obstacle, first_violation, per_obstacle);
+  });
+}
+
+int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearance) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_evaluate_path: NULL argument");
+    h->use_device();
+    if (h->has_best_h != 1 || h->D.P > 1) {   // (has_best_h speaks for population 0: read every population's flag back)
+      sync(h);
+      std::vector<int32_t> hb((size_t)h->D.P, 0);
+      h->download(hb.data(), h->D.has_best, hb.size());
+      if (h->has_best_h < 0) h->has_best_h = hb[0] ? 1 : 0;
+      for (int32_t v : hb)
+        if (!v) fail(PMAF_ERR_STATE, "pmaf_evaluate_path: no agent has been selected yet (call pmaf_evaluate / pmaf_tick first)");
+    }
+    evaluate_paths(h, obstacles, 0.0, true, clearance, nullptr, nullptr, nullptr, nullptr);
   });
 }
 

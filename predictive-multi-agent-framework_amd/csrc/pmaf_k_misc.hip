@@ -7,6 +7,7 @@
 //   k_score         re-scores stored paths (before the first rollout / other workspace gains).
 //   k_link_force    CfAgent::bodyForce (B/src/cf_agent.cpp:229-234).
 //   k_winner        packs winner records for sharded runs.
+//   k_audit_track, k_path_audit (pmaf_path_audit.hpp)  the predicted paths against a live obstacle list.
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -15,6 +16,7 @@
 #include "pmaf_device.hpp"
 #include "pmaf_rollout_w64.hpp"
 #include "pmaf_rollout_grp.hpp"
+#include "pmaf_path_audit.hpp"
 
 using namespace pmaf;
 
@@ -989,6 +991,11 @@ void pmaf_k_launch_set_agents(const DevView &D, const double *pos, const double 
 
 void pmaf_k_launch_eval_obstacle_distance(const DevView &D, const double *obs, double *out, hipStream_t s) {
   hipLaunchKernelGGL(k_eval_obstacle_distance, dim3((D.P * D.N + 255) / 256), dim3(256), 0, s, D, obs, out);
+}
+
+void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *track, hipStream_t s) {
+  hipLaunchKernelGGL(k_audit_track, dim3((D.P * D.n_obs + 63) / 64), dim3(64), 0, s, D.P, D.n_obs, D.cap, D.C.dt, A.obs, track);
+  hipLaunchKernelGGL(k_path_audit, dim3((unsigned)(A.only_best ? 1 : D.N), (unsigned)D.P), dim3(64 * PMAF_AUDIT_WAVES), 0, s, D, A);
 }
 
 hipError_t pmaf_k_set_lds_limits(size_t lds_manager, size_t lds_rollout) {

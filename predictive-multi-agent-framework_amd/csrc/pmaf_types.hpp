@@ -176,6 +176,18 @@ struct PlanArgs {
   int32_t *calls_out;      // [P] cfPlanner calls made for the `only` agent (moveAgent), may be NULL
 };
 
+// path audit (pmaf_evaluate_paths / pmaf_evaluate_path): k_audit_track + k_path_audit, pmaf_path_audit.hpp
+struct AuditArgs {
+  const double *obs;        // [P][7][n_obs] SoA: the caller's live obstacle list
+  const double *track;      // [P][cap][3][n_obs] obstacle positions at every step (k_audit_track)
+  double margin;            // first_violation: the first step with a clearance below it
+  int group_log2;           // lanes per path point = 2^group_log2 = min(64, next power of two >= n_obs)
+  int only_best;            // 1: the selected agent of every population only (outputs [P]), 0: every agent ([P][N])
+  double *clearance;        // [P][N]
+  int32_t *step, *obstacle, *first_violation;   // [P][N], each may be NULL
+  double *per_obstacle;     // [P][N][n_obs] or NULL
+};
+
 // ---------------------------------------------------------------------------
 // launch interface: implemented in pmaf_k_w64.hip / pmaf_k_grp.hip / pmaf_k_misc.hip
 // ---------------------------------------------------------------------------
@@ -213,5 +225,8 @@ bool pmaf_k_launch_plan_steps(const DevView &D, const PlanArgs &A, int lpa, int 
 void pmaf_k_launch_set_agents(const DevView &D, const double *pos, const double *vel, hipStream_t s);
 // CfAgent::evalObstacleDistance for every agent: obs [P][7][n_obs] SoA, out [P][N]
 void pmaf_k_launch_eval_obstacle_distance(const DevView &D, const double *obs, double *out, hipStream_t s);
+// the audit's two kernels back to back: the obstacle track of A.obs into `track` (= A.track), then one block per
+// (agent, population) -- or per population with A.only_best
+void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *track, hipStream_t s);
 // opt the kernels that take dynamic LDS into more than the 64 KB default
 hipError_t pmaf_k_set_lds_limits(size_t lds_manager, size_t lds_rollout);

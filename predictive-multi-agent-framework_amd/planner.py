@@ -63,6 +63,8 @@ SYMBOLS = {
     "pmaf_set_agent_positions": (C.c_int, [_V, _dp]),
     "pmaf_set_agent_pos_and_vels": (C.c_int, [_V, _dp, _dp]),
     "pmaf_eval_obstacle_distance": (C.c_int, [_V, _dp, _dp]),
+    "pmaf_evaluate_paths": (C.c_int, [_V, _dp, C.c_double, _dp, _ip, _ip, _ip, _dp]),
+    "pmaf_evaluate_path": (C.c_int, [_V, _dp, _dp]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -321,6 +323,27 @@ class PmafPlanner:
         out = np.zeros((self.P, self.N))
         self._chk(self.L.pmaf_eval_obstacle_distance(self._h, _p(self._obs(obstacles)), _p(out)))
         return self._sq(out)
+
+    # -- path audit (CfManager::evaluatePath, declared and never defined by the reference) --
+    def evaluate_paths(self, obstacles, margin=0.0, per_obstacle=False):
+        """every agent's current predicted path against the live obstacle list (pmaf_evaluate_paths): a dict of
+        clearance [P][N], step, obstacle, first_violation (int32) and, on request, per_obstacle [P][N][n_obs]"""
+        o = self._obs(obstacles)
+        out = {"clearance": np.zeros((self.P, self.N))}
+        for k in ("step", "obstacle", "first_violation"):
+            out[k] = np.zeros((self.P, self.N), dtype=np.int32)
+        po = np.zeros((self.P, self.N, self.n_obs)) if per_obstacle else None
+        self._chk(self.L.pmaf_evaluate_paths(self._h, _p(o), float(margin), _p(out["clearance"]), _pi(out["step"]),
+                                             _pi(out["obstacle"]), _pi(out["first_violation"]), _p(po)))
+        if per_obstacle:
+            out["per_obstacle"] = po
+        return {k: self._sq(v) for k, v in out.items()}
+
+    def evaluate_path(self, obstacles):
+        """clearance of the SELECTED agent's current path (pmaf_evaluate_path); PmafError -3 before any selection"""
+        out = np.zeros(self.P)
+        self._chk(self.L.pmaf_evaluate_path(self._h, _p(self._obs(obstacles)), _p(out)))
+        return float(out[0]) if self.P == 1 else out
 
     def link_force(self, link_pos, k_r_force, obstacles, pop=0):
         lp, k, o = _d(link_pos), _d(k_r_force), self._obs(obstacles)
