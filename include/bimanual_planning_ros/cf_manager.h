@@ -62,6 +62,15 @@ struct PathAudit {
   std::vector<int> first_violation;  // first path point with a clearance below the margin; the path's size if none
 };
 
+// result of CfManager::crossAudit: this manager's predicted paths against another arm's (pmaf.h, "cross audit")
+struct CrossAudit {
+  int n_agents = 0, n_other = 0;
+  std::vector<double> clearance;  // [n_agents][n_other] least distance of the two paths, step by step, minus separation [m]
+  std::vector<int> step;          // ... and the step at which it is reached (-1: an empty path, or nothing comparable)
+  double at(int agent, int other) const { return clearance.at((size_t)agent * n_other + other); }
+  int step_at(int agent, int other) const { return step.at((size_t)agent * n_other + other); }
+};
+
 class CfManager {
   pmaf_planner *h_ = nullptr;
   int n_agents_ = 0;
@@ -453,6 +462,35 @@ class CfManager {
     r.step.assign(st.begin(), st.end());
     r.obstacle.assign(ob.begin(), ob.end());
     r.first_violation.assign(fv.begin(), fv.end());
+    return r;
+  }
+  // The other arm of a bimanual node is a second CfManager: every predicted path of THIS manager against every path of
+  // `other_paths` (the other manager's getPredictedPaths(), or its selected path alone), both on the same step grid, an
+  // ended path held at its last point (pmaf_cross_audit_tracks; no reference equivalent). separation = the sum of the
+  // two bodies' radii. std::out_of_range for a path longer than max_prediction_steps or an empty list.
+  CrossAudit crossAudit(const std::vector<std::vector<Vector3d>> &other_paths, const double separation) {
+    require();
+    if (other_paths.empty()) throw std::out_of_range("crossAudit: no paths given");
+    const size_t n = other_paths.size(), row = (size_t)cap_ * 3;
+    std::vector<double> tracks(n * row, 0.0);
+    std::vector<int32_t> len(n);
+    for (size_t j = 0; j < n; ++j) {
+      if (other_paths[j].size() > (size_t)cap_) throw std::out_of_range("crossAudit: a path is longer than max_prediction_steps");
+      len[j] = (int32_t)other_paths[j].size();
+      for (size_t k = 0; k < other_paths[j].size(); ++k) {
+        const Vector3d &q = other_paths[j][k];
+        double *r = &tracks[j * row + k * 3];
+        r[0] = q.x(); r[1] = q.y(); r[2] = q.z();
+      }
+    }
+    CrossAudit r;
+    r.n_agents = n_agents_;
+    r.n_other = (int)n;
+    r.clearance.resize((size_t)n_agents_ * n);
+    std::vector<int32_t> st((size_t)n_agents_ * n);
+    check(pmaf_cross_audit_tracks(h_, 0, (int32_t)n, tracks.data(), len.data(), separation, r.clearance.data(), st.data()),
+          "crossAudit");
+    r.step.assign(st.begin(), st.end());
     return r;
   }
   // the whole planCallback sequence (B/src/panda_bimanual_control.cpp:336-352)

@@ -301,6 +301,60 @@ int pmaf_evaluate_paths(pmaf_planner *h, const double *obstacles, double margin,
  * current path only; clearance [P]. PMAF_ERR_STATE before the first selection (pmaf_evaluate / pmaf_tick). */
 int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearance);
 
+/* ---- cross audit: two sets of predicted paths against each other; the pair pick (exports added under ABI 7) ----
+ * A bimanual planner runs one population per arm. What one arm's rollouts see of the other is a single sphere at the
+ * other arm's last published set-point (the trailing repulsive obstacle); pmaf_evaluate scores each population alone,
+ * and pmaf_evaluate_paths holds paths against spheres on straight constant-velocity tracks, which the other arm's
+ * predicted path is not. These calls hold the two arms' candidate paths against each other, step by step (SURVEY.md
+ * 8(e): the other arm's "winning path, sampled at the same step"). No reference equivalent.
+ * Two path sets of one handle share dt and max_prediction_steps (cap). Path i of set A has the points x_0 .. x_{n-1},
+ * path j of set B the points y_0 .. y_{m-1}; both rollouts start at the same tick, so step k of both is one instant.
+ *   hold:       a path that has ended (goal guard, the stepping calls) stays at its last point:
+ *               xh_k = x_{min(k, n-1)}, yh_k = y_{min(k, m-1)}, for k < K = max(n, m)
+ *   empty:      n == 0 or m == 0: clearance +infinity, step -1
+ *   d2(k)     = dot(xh_k - yh_k, xh_k - yh_k) in the build's dot association (pmaf_eval_order), every operation
+ *               rounded, nothing fused
+ *   step(i,j) = argmin over k of d2(k), found with a strict `<` from +infinity, k ascending: ties go to the smallest
+ *               k, a NaN never wins; -1 if none won
+ *   clearance(i,j) = sqrt(d2(step)) - separation, +infinity if none won. separation = the caller's sum of the two
+ *               bodies' radii (for shard.DualArmCoupling: pmaf_params.radius + its self-collision radius); no floor,
+ *               no cap, negative = penetration.
+ * The minimum is defined on d2, not on its root: sqrt is correctly rounded and therefore monotone, so clearance equals
+ * the minimum over k of sqrt(d2(k)) - separation bit for bit; only the tie rule of `step` depends on the choice.
+ * All three calls wait for the running rollout like the getters of its results and change no planner state (a tick
+ * sequence with these calls in between is bit-identical to one without).
+ *
+ * pmaf_cross_audit: set A = population pop_a's CURRENT paths, set B = population pop_b's, read where they lie on the
+ * device. clearance [N][N] (row i = agent i of pop_a), step [N][N] or NULL. PMAF_ERR_INVALID for pop_a == pop_b or an
+ * index outside [0, P). */
+int pmaf_cross_audit(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double *clearance, int32_t *step);
+/* Set B from the caller: the other arm when it lives in another handle or on another GPU (its selected path is on
+ * every rank in the winner records; through the facade, the paths of a second CfManager). tracks
+ * [n_tracks][cap][3] with cap = max_prediction_steps, n_track_points [n_tracks]; rows past a track's count are not
+ * read, the others are range-checked like every input. clearance [N][n_tracks], step likewise or NULL.
+ * PMAF_ERR_INVALID for n_tracks <= 0 or a count outside [0, cap]. */
+int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                            const int32_t *n_track_points, double separation, double *clearance, int32_t *step);
+/* The cheapest pair of candidates that keeps its distance. cost_a[i], cost_b[j] = what pmaf_get_costs returns at this
+ * moment for the two populations (read from the same device array behind the same wait: whatever that getter reports
+ * in a state of the handle -- zeros before the first pmaf_evaluate / pmaf_tick made cost parameters known -- is what
+ * this call uses, and it fails where and how that getter fails).
+ *   feasible(i,j) iff clearance(i,j) >= margin                 (false for NaN, true for +infinity)
+ *   among feasible pairs: the minimum of S = cost_a[i] + cost_b[j] (one rounded add), strict `<` from +infinity in
+ *   row-major order: ties go to the smallest i, then the smallest j; a NaN sum never wins. -> *feasible = 1
+ *   if no pair won: *feasible = 0 and the pair of the greatest clearance, strict `>` from -infinity in row-major order;
+ *   if still none won: pair = (-1, -1).
+ * pair [2] = (i, j); *pair_cost = S and *pair_clearance = clearance of the returned pair, both NaN for (-1, -1). The
+ * matrix stays on the device between the audit and the reduction; only these results come back. The call selects
+ * NOTHING in the handle: the caller applies the pair through what exists -- pmaf_move_real's agent_id (or
+ * pmaf_set_best). Intended five-call tick of a bimanual node, both arms in one handle:
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_pair -> pmaf_move_real(agent_id = pair) -> pmaf_reset_agents -> pmaf_start
+ * Right after pmaf_tick the call is pointless: that call has already moved, reset and restarted, so the paths in the
+ * handle belong to the NEW rollout while the costs still describe the old one. Hysteresis over pairs is the caller's
+ * (it has both costs and can apply evaluateAgents' 0.9 rule). */
+int pmaf_select_pair(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t *pair,
+                     double *pair_cost, double *pair_clearance, int32_t *feasible);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

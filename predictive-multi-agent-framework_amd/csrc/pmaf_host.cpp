@@ -198,6 +198,10 @@ struct pmaf_planner {
   // outputs on the device, the outputs' pinned host mirror (one device-to-host copy per call)
   char *d_audit = nullptr, *h_audit = nullptr;
   size_t audit_bytes = 0;
+  // pmaf_cross_audit / pmaf_cross_audit_tracks / pmaf_select_pair scratch, grown on demand: the clearance matrix and the
+  // step matrix, the pair reduction's partials and result, the caller's tracks and their lengths
+  char *d_xaudit = nullptr;
+  size_t xaudit_bytes = 0;
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};
@@ -1061,6 +1065,7 @@ int pmaf_destroy(pmaf_planner *h) {
   if (h->h_link) (void)hipHostFree(h->h_link);
   if (h->d_audit) (void)hipFree(h->d_audit);
   if (h->h_audit) (void)hipHostFree(h->h_audit);
+  if (h->d_xaudit) (void)hipFree(h->d_xaudit);
   for (auto &e : h->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto &e : h->ev_inflight) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   if (h->ev_mgr) (void)hipEventDestroy(h->ev_mgr);
@@ -1538,6 +1543,142 @@ int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearan
         if (!v) fail(PMAF_ERR_STATE, "pmaf_evaluate_path: no agent has been selected yet (call pmaf_evaluate / pmaf_tick first)");
     }
     evaluate_paths(h, obstacles, 0.0, true, clearance, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+
+// ---- cross audit: two path sets against each other, step by step; the pair pick (include/pmaf.h) ----
+// Device scratch of one call: clearance [n_a][n_b] | partials | result | tracks [n_tracks][cap][3] | step [n_a][n_b] |
+// track lengths [n_tracks] (doubles first: every part stays 8-byte aligned)
+struct XAuditBuf {
+  double *clearance;
+  PairBest *partial;
+  PairResult *result;
+  double *tracks;
+  int32_t *step, *track_len;
+};
+static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks) {
+  const size_t pairs = n_a * n_b;
+  if (pairs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "cross audit: the number of pairs must stay below 2^31");
+  const size_t b_clr = sizeof(double) * pairs, b_part = sizeof(PairBest) * PMAF_XAUDIT_PARTIALS, b_res = sizeof(PairResult);
+  const size_t b_trk = sizeof(double) * n_tracks * (size_t)h->D.cap * 3, b_step = (sizeof(int32_t) * pairs + 7) & ~(size_t)7;
+  const size_t total = b_clr + b_part + b_res + b_trk + b_step + sizeof(int32_t) * n_tracks;
+  if (total > h->xaudit_bytes) {
+    if (h->d_xaudit) { (void)hipFree(h->d_xaudit); h->d_xaudit = nullptr; }
+    h->xaudit_bytes = 0;
+    HIP_CHECK(hipMalloc((void **)&h->d_xaudit, total));
+    h->xaudit_bytes = total;
+  }
+  XAuditBuf B;
+  char *p = h->d_xaudit;
+  B.clearance = reinterpret_cast<double *>(p); p += b_clr;
+  B.partial = reinterpret_cast<PairBest *>(p); p += b_part;
+  B.result = reinterpret_cast<PairResult *>(p); p += b_res;
+  B.tracks = reinterpret_cast<double *>(p); p += b_trk;
+  B.step = reinterpret_cast<int32_t *>(p); p += b_step;
+  B.track_len = reinterpret_cast<int32_t *>(p);
+  return B;
+}
+
+// population pop_a's paths against population pop_b's where they lie; the matrix stays in the scratch
+static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, bool want_step,
+                                         const char *who) {
+  const DevView &D = h->D;
+  if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
+    fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
+  check_range(&separation, 1, "separation");
+  h->use_device();
+  sync(h);   // behind the running rollout, like the getters of its results
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0);
+  CrossAuditArgs A{};
+  A.paths_a = D.paths + (size_t)pop_a * D.N * D.cap * 3;
+  A.paths_b = D.paths + (size_t)pop_b * D.N * D.cap * 3;
+  A.len_a = D.n_points + (size_t)pop_a * D.N;
+  A.len_b = D.n_points + (size_t)pop_b * D.N;
+  A.n_a = A.n_b = D.N;
+  A.cap = D.cap;
+  A.separation = separation;
+  A.clearance = B.clearance;
+  A.step = want_step ? B.step : nullptr;
+  pmaf_k_launch_cross_audit(A, h->stream);
+  HIP_CHECK(hipGetLastError());
+  return B;
+}
+
+int pmaf_cross_audit(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double *clearance, int32_t *step) {
+  return guarded([&] {
+    REQUIRE(h && clearance, "pmaf_cross_audit: NULL argument");
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, step != nullptr, "pmaf_cross_audit");
+    const size_t pairs = (size_t)h->D.N * h->D.N;
+    if (step) HIP_CHECK(hipMemcpyAsync(step, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    h->download(clearance, B.clearance, pairs);
+  });
+}
+
+int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                            const int32_t *n_track_points, double separation, double *clearance, int32_t *step) {
+  return guarded([&] {
+    REQUIRE(h && tracks && n_track_points && clearance, "pmaf_cross_audit_tracks: NULL argument");
+    const DevView &D = h->D;
+    REQUIRE(pop >= 0 && pop < D.P, "pmaf_cross_audit_tracks: population out of range");
+    REQUIRE(n_tracks > 0, "pmaf_cross_audit_tracks: n_tracks must be > 0");
+    check_range(&separation, 1, "separation");
+    // rows past a track's count are neither checked nor copied
+    const size_t row = (size_t)D.cap * 3;
+    std::vector<double> packed((size_t)n_tracks * row, 0.0);
+    for (int32_t t = 0; t < n_tracks; t++) {
+      REQUIRE(n_track_points[t] >= 0 && n_track_points[t] <= D.cap, "pmaf_cross_audit_tracks: a track's point count must be in [0, max_prediction_steps]");
+      check_range(tracks + t * row, (size_t)n_track_points[t] * 3, "tracks");
+      std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
+    }
+    h->use_device();
+    sync(h);
+    const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks);
+    HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
+    h->upload(B.tracks, packed.data(), packed.size());
+    CrossAuditArgs A{};
+    A.paths_a = D.paths + (size_t)pop * D.N * D.cap * 3;
+    A.paths_b = B.tracks;
+    A.len_a = D.n_points + (size_t)pop * D.N;
+    A.len_b = B.track_len;
+    A.n_a = D.N;
+    A.n_b = n_tracks;
+    A.cap = D.cap;
+    A.separation = separation;
+    A.clearance = B.clearance;
+    A.step = step ? B.step : nullptr;
+    pmaf_k_launch_cross_audit(A, h->stream);
+    HIP_CHECK(hipGetLastError());
+    const size_t pairs = (size_t)D.N * n_tracks;
+    if (step) HIP_CHECK(hipMemcpyAsync(step, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    h->download(clearance, B.clearance, pairs);
+  });
+}
+
+int pmaf_select_pair(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t *pair,
+                     double *pair_cost, double *pair_clearance, int32_t *feasible) {
+  return guarded([&] {
+    REQUIRE(h && pair && pair_cost && pair_clearance && feasible, "pmaf_select_pair: NULL argument");
+    check_range(&margin, 1, "margin");
+    // the costs are read where pmaf_get_costs reads them (DevView::costs, behind the same wait), so both calls see the
+    // same values in every state of the handle
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, false, "pmaf_select_pair");
+    const DevView &D = h->D;
+    PairArgs A{};
+    A.clearance = B.clearance;
+    A.cost_a = D.costs + (size_t)pop_a * D.N;
+    A.cost_b = D.costs + (size_t)pop_b * D.N;
+    A.n_a = A.n_b = D.N;
+    A.margin = margin;
+    A.partial = B.partial;
+    A.result = B.result;
+    pmaf_k_launch_pair_reduce(A, h->stream);
+    HIP_CHECK(hipGetLastError());
+    PairResult r{};
+    h->download(&r, B.result, 1);
+    pair[0] = r.i; pair[1] = r.j;
+    *pair_cost = r.cost;
+    *pair_clearance = r.clearance;
+    *feasible = r.feasible;
   });
 }
 

@@ -8,6 +8,7 @@
 //   k_link_force    CfAgent::bodyForce (B/src/cf_agent.cpp:229-234).
 //   k_winner        packs winner records for sharded runs.
 //   k_audit_track, k_path_audit (pmaf_path_audit.hpp)  the predicted paths against a live obstacle list.
+//   k_cross_audit, k_pair_reduce, k_pair_final (pmaf_cross_audit.hpp)  two path sets against each other, the pair pick.
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -17,6 +18,7 @@
 #include "pmaf_rollout_w64.hpp"
 #include "pmaf_rollout_grp.hpp"
 #include "pmaf_path_audit.hpp"
+#include "pmaf_cross_audit.hpp"
 
 using namespace pmaf;
 
@@ -996,6 +998,19 @@ void pmaf_k_launch_eval_obstacle_distance(const DevView &D, const double *obs, d
 void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *track, hipStream_t s) {
   hipLaunchKernelGGL(k_audit_track, dim3((D.P * D.n_obs + 63) / 64), dim3(64), 0, s, D.P, D.n_obs, D.cap, D.C.dt, A.obs, track);
   hipLaunchKernelGGL(k_path_audit, dim3((unsigned)(A.only_best ? 1 : D.N), (unsigned)D.P), dim3(64 * PMAF_AUDIT_WAVES), 0, s, D, A);
+}
+
+void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s) {
+  const dim3 grid((unsigned)((A.n_b + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE), (unsigned)((A.n_a + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE));
+  hipLaunchKernelGGL(k_cross_audit, grid, dim3(PMAF_XAUDIT_THREADS), 0, s, A);
+}
+
+void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s) {
+  const long long total = (long long)A.n_a * A.n_b;
+  long long nb = (total + PMAF_XAUDIT_THREADS - 1) / PMAF_XAUDIT_THREADS;
+  nb = nb < PMAF_XAUDIT_PARTIALS ? nb : PMAF_XAUDIT_PARTIALS;
+  hipLaunchKernelGGL(k_pair_reduce, dim3((unsigned)nb), dim3(PMAF_XAUDIT_THREADS), 0, s, A);
+  hipLaunchKernelGGL(k_pair_final, dim3(1), dim3(PMAF_XAUDIT_THREADS), 0, s, A, (int)nb);
 }
 
 hipError_t pmaf_k_set_lds_limits(size_t lds_manager, size_t lds_rollout) {

@@ -188,6 +188,36 @@ struct AuditArgs {
   double *per_obstacle;     // [P][N][n_obs] or NULL
 };
 
+// cross audit (pmaf_cross_audit / pmaf_cross_audit_tracks / pmaf_select_pair): pmaf_cross_audit.hpp
+struct CrossAuditArgs {
+  const double *paths_a, *paths_b;   // [n_a][cap][3], [n_b][cap][3]: set A = a population's paths, set B = another
+                                     // population's or the caller's uploaded tracks
+  const int32_t *len_a, *len_b;      // [n_a], [n_b] points per path, 0 .. cap
+  int n_a, n_b, cap;
+  double separation;
+  double *clearance;                 // [n_a][n_b]
+  int32_t *step;                     // [n_a][n_b] or NULL
+};
+// running results of the pair reduction: the cheapest feasible sum and the greatest clearance, each with its row-major
+// index (0x7fffffff: nothing won). The clearance is carried NEGATED so that both are minima under (value, index).
+struct PairBest {
+  double s, nc;
+  int32_t si, ci;
+};
+#define PMAF_XAUDIT_PARTIALS 256   // blocks of the pair reduction's first stage (= threads of its second)
+struct PairResult {
+  double cost, clearance;
+  int32_t i, j, feasible, pad;
+};
+struct PairArgs {
+  const double *clearance;           // [n_a][n_b] on the device (k_cross_audit's output)
+  const double *cost_a, *cost_b;     // [n_a], [n_b]: the populations' rows of DevView::costs
+  int n_a, n_b;
+  double margin;
+  PairBest *partial;                 // [PMAF_XAUDIT_PARTIALS] first-stage results
+  PairResult *result;
+};
+
 // ---------------------------------------------------------------------------
 // launch interface: implemented in pmaf_k_w64.hip / pmaf_k_grp.hip / pmaf_k_misc.hip
 // ---------------------------------------------------------------------------
@@ -228,5 +258,9 @@ void pmaf_k_launch_eval_obstacle_distance(const DevView &D, const double *obs, d
 // the audit's two kernels back to back: the obstacle track of A.obs into `track` (= A.track), then one block per
 // (agent, population) -- or per population with A.only_best
 void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *track, hipStream_t s);
+// k_cross_audit on a grid of (n_b, n_a) / 32 tiles
+void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s);
+// the two stages of the pair reduction back to back
+void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s);
 // opt the kernels that take dynamic LDS into more than the 64 KB default
 hipError_t pmaf_k_set_lds_limits(size_t lds_manager, size_t lds_rollout);

@@ -65,6 +65,9 @@ SYMBOLS = {
     "pmaf_eval_obstacle_distance": (C.c_int, [_V, _dp, _dp]),
     "pmaf_evaluate_paths": (C.c_int, [_V, _dp, C.c_double, _dp, _ip, _ip, _ip, _dp]),
     "pmaf_evaluate_path": (C.c_int, [_V, _dp, _dp]),
+    "pmaf_cross_audit": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, _dp, _ip]),
+    "pmaf_cross_audit_tracks": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, _dp, _ip]),
+    "pmaf_select_pair": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_double, _ip, _dp, _dp, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -344,6 +347,34 @@ class PmafPlanner:
         out = np.zeros(self.P)
         self._chk(self.L.pmaf_evaluate_path(self._h, _p(self._obs(obstacles)), _p(out)))
         return float(out[0]) if self.P == 1 else out
+
+    # -- cross audit: two populations' predicted paths against each other, the pair pick --
+    def cross_audit(self, pop_a, pop_b, separation, step=False):
+        """clearance [N][N] of population pop_a's current paths against pop_b's (pmaf_cross_audit); with step=True
+        (clearance, step), step int32 [N][N]"""
+        clr = np.zeros((self.N, self.N))
+        st = np.zeros((self.N, self.N), dtype=np.int32) if step else None
+        self._chk(self.L.pmaf_cross_audit(self._h, int(pop_a), int(pop_b), float(separation), _p(clr), _pi(st)))
+        return (clr, st) if step else clr
+
+    def cross_audit_tracks(self, pop, tracks, n_track_points, separation, step=False):
+        """population pop's current paths against the caller's tracks [n_tracks][cap][3] of n_track_points [n_tracks]
+        points each (pmaf_cross_audit_tracks): clearance [N][n_tracks], with step=True (clearance, step)"""
+        n = np.ascontiguousarray(n_track_points, dtype=np.int32).reshape(-1)
+        tr = _d(tracks).reshape(n.size, self.cap, 3)
+        clr = np.zeros((self.N, n.size))
+        st = np.zeros((self.N, n.size), dtype=np.int32) if step else None
+        self._chk(self.L.pmaf_cross_audit_tracks(self._h, int(pop), n.size, _p(tr), _pi(n), float(separation), _p(clr), _pi(st)))
+        return (clr, st) if step else clr
+
+    def select_pair(self, pop_a, pop_b, separation, margin):
+        """the cheapest pair (i of pop_a, j of pop_b) whose paths keep `margin` of clearance (pmaf_select_pair): a dict
+        of pair (i, j), cost, clearance, feasible; selects nothing in the handle"""
+        pair = np.zeros(2, dtype=np.int32)
+        cost, clr, feas = C.c_double(0), C.c_double(0), C.c_int32(0)
+        self._chk(self.L.pmaf_select_pair(self._h, int(pop_a), int(pop_b), float(separation), float(margin), _pi(pair),
+                                          C.byref(cost), C.byref(clr), C.byref(feas)))
+        return {"pair": (int(pair[0]), int(pair[1])), "cost": cost.value, "clearance": clr.value, "feasible": bool(feas.value)}
 
     def link_force(self, link_pos, k_r_force, obstacles, pop=0):
         lp, k, o = _d(link_pos), _d(k_r_force), self._obs(obstacles)

@@ -134,6 +134,28 @@ class DualArmCoupling:
         self.obstacles = obs
         return obs
 
+    def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None):
+        """One tick of both arms as populations 0 / 1 of ONE handle, the two winners picked TOGETHER: the node's
+        five-call sequence with pmaf_select_pair in it (include/pmaf.h "cross audit") --
+        stop -> evaluate -> select_pair -> move_real(agent_id = the pair) -> reset -> start. The pair is the cheapest
+        (cost_0[i] + cost_1[j]) whose predicted paths keep `margin` between two spheres of agent_radius and the
+        self-collision radius; without such a pair, the one with the greatest clearance. The rollouts themselves still
+        see the other arm only as the sphere at its last set-point (coupled_obstacles). Returns a dict: pair (i, j),
+        feasible, cost, clearance, positions [2][3] (the new set-points)."""
+        assert planner.P == 2, "pair_tick drives the two populations of one handle"
+        planner.stop()
+        best = planner.evaluate(cost_gains, ws)
+        out = planner.select_pair(0, 1, agent_radius + self.radius, margin)
+        pair = out["pair"] if out["pair"][0] >= 0 else tuple(int(b) for b in best)   # no comparable pair: each arm's own
+        obs = self.coupled_obstacles(planner.real_state()[0], advance)
+        planner.move_real(obs, dt, 1, np.asarray(pair, dtype=np.int32))
+        pos, vel, _ = planner.real_state()
+        planner.reset_agents(pos, vel, obs)
+        planner.start()
+        out["pair"] = tuple(int(v) for v in pair)
+        out["positions"] = np.array(pos, copy=True)
+        return out
+
 
 def connect_peers(planner, dist, world, rank):
     """Peer mailboxes of a multi-process run (include/pmaf.h "peer mailboxes"):
