@@ -31,6 +31,7 @@ class Stats:
         self.components = 0
         self.seen = {}
         self.failures = []
+        self.selections = 0       # compared "best index" samples (check_evaluate)
         self.notes = []           # callables returning extra report lines (tests/hp_anchored.py)
 
     def merge_seen(self, seen):
@@ -147,7 +148,11 @@ def snapshot(planner, pop=None):
 
 def check_evaluate(A, st, scene, pre, costs, best, agents):
     """CfManager::evaluateAgents on the rollout in `pre`: every sampled agent's cost; the selected index too when all
-    agents are sampled and the argmin / hysteresis are decided"""
+    agents are sampled and the argmin / hysteresis are decided (counted in st.selections). Two agents' fp64 costs are
+    known to be the same bits when their inputs are (the same path and min_obs_dist). Two costs the reference computed
+    with bound 0 and equal value are taken as a tie too (the all-zero costs of tests/hp_select.py need this): that is safe
+    because each of them has just been held to the planner's cost with bound 0 by st.check above -- a planner whose
+    operation order rounds where the reference's does not fails there, before the selection is looked at"""
     N = int(scene["n_agents"])
     qc = {}
     for i in agents:
@@ -158,11 +163,13 @@ def check_evaluate(A, st, scene, pre, costs, best, agents):
             qc[i] = q
         st.run(A, one)
     if len(qc) == N:
-        keys = [(pre["paths"][i, :pre["n"][i]].tobytes(), float(pre["min_obs_dist"][i])) for i in range(N)]
+        keys = [("exact", qc[i].v) if qc[i].e == 0.0 else
+                (pre["paths"][i, :pre["n"][i]].tobytes(), float(pre["min_obs_dist"][i])) for i in range(N)]
 
         def sel():
             st.expect("best index", hp.select_best(A, [qc[i] for i in range(N)], pre["best_id"], keys), best)
-        st.run(A, sel)
+        if st.run(A, sel):
+            st.selections += 1
 
 
 def check_real(A, st, scene, pre, post, init_pos, obs_rows, best):
@@ -222,21 +229,28 @@ def coupled_rows(obs_rows, pre, coupling):
     return out
 
 
-def shadow_tick(planner, scene, obs_rows, init_pos, A, st, agents=None, rollouts=None, coupling=None):
+def shadow_tick(planner, scene, obs_rows, init_pos, A, st, agents=None, rollouts=None, coupling=None, eval_agents=None,
+                eval_stats=None):
     """one planCallback tick (evaluate, move the real agent, reset, roll out; B/src/panda_bimanual_control.cpp:336-352)
     shadowed: costs from the previous paths, the real agent's step from the previous real state with the agent selected
     this tick, every sampled agent's rollout from the new real state. rollouts: the rollout checker (check_rollouts, or
     tests/hp_anchored.py's walker). scene a list of P scene dicts: a P-population planner, every population shadowed
-    (obs_rows [P, M, 7], init_pos [P, 3], coupling as in coupled_rows); returns the per-population best indices."""
+    (obs_rows [P, M, 7], init_pos [P, 3], coupling as in coupled_rows); returns the per-population best indices.
+    eval_agents: agents whose cost is compared IN ADDITION to those of `agents` (whose rollouts are checked), into
+    eval_stats (default: st) -- a separate Stats keeps the undecidable share of st what it was; "all" compares every
+    agent's cost and therefore the selected index too."""
     rollouts = check_rollouts if rollouts is None else rollouts
     if isinstance(scene, dict):
         agents = list(range(int(scene["n_agents"]))) if agents is None else list(agents)
+        est = st if eval_stats is None else eval_stats
         obs_rows = np.asarray(obs_rows, dtype=np.float64)
         pre = snapshot(planner)
         best = int(planner.tick(obs_rows, scene["dt"], scene["cost_gains"], scene["ws_limits"]))
         post = snapshot(planner)
         assert post["best_id"] == best + 1
         check_evaluate(A, st, scene, pre, post["costs"], best, agents)
+        if eval_agents is not None:
+            check_evaluate(A, est, scene, pre, post["costs"], best, _eval_agents(eval_agents, scene))
         check_real(A, st, scene, pre, post, init_pos, obs_rows, best)
         rollouts(A, st, scene, post["real_pos"], post["real_vel"], post["real_known"], pre["rot_vecs"],
                  pre["success"], post, obs_rows, init_pos, agents)
@@ -255,9 +269,16 @@ def shadow_tick(planner, scene, obs_rows, init_pos, A, st, agents=None, rollouts
         ag = list(range(int(sc["n_agents"]))) if agents is None else list(agents)
         assert post[p]["best_id"] == best[p] + 1, (p, post[p]["best_id"], best[p])
         check_evaluate(A, st, sc, pre[p], post[p]["costs"], best[p], ag)
+        if eval_agents is not None:
+            check_evaluate(A, st if eval_stats is None else eval_stats, sc, pre[p], post[p]["costs"], best[p],
+                           _eval_agents(eval_agents, sc))
         check_real(A, st, sc, pre[p], post[p], init_pos[p], rows[p], best[p])
         _call_rollouts(rollouts, A, st, sc, pre[p], post[p], rows[p], init_pos[p], ag, "pop %d " % p)
     return best
+
+
+def _eval_agents(eval_agents, scene):
+    return list(range(int(scene["n_agents"]))) if isinstance(eval_agents, str) and eval_agents == "all" else list(eval_agents)
 
 
 def _call_rollouts(rollouts, A, st, sc, pre, post, rows, init_pos, agents, label):

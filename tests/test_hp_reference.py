@@ -255,17 +255,19 @@ def _task_scene(scenes, name):
     return scenes.scene_from_record(recs[name], name)
 
 
-def _anchored_ticks(orc, scenes, scene, n_ticks, name, agents, frac, dynamic=False, walk_from=0, policy="xact"):
+def _anchored_ticks(orc, scenes, scene, n_ticks, name, agents, frac, dynamic=False, walk_from=0, policy="xact",
+                    eval_agents=None):
     """n_ticks planCallback ticks of the oracle; from tick walk_from on every sampled agent's rollout is walked"""
     A = hp.Arith(policy)
     st = sh.Stats(name)
+    st.evaluation = sh.Stats(name + ", every cost and the selection")    # (its own counts: st's cap is unchanged)
     pl = orc.OraclePlanner(scene, mgr_init_pos=scene["start"])
     try:
         ip = sh.start(pl, scene, init_pos=scene["start"] + np.array([0.0, 0.0, -0.25]), real_pos=scene["start"])
         obs = scene["obstacles"].copy()
         for t in range(n_ticks):
             sh.shadow_tick(pl, scene, obs, ip, A, st, agents=agents if t >= walk_from else [],
-                           rollouts=ha.walker(frac, seed=t))
+                           rollouts=ha.walker(frac, seed=t), eval_agents=eval_agents, eval_stats=st.evaluation)
             if dynamic:
                 obs = scenes.advance_live_obstacles(obs)
     finally:
@@ -348,7 +350,9 @@ def _pop_case(orc, scenes, name, coupling=None, swap_goals=False, n_ticks=3):
 
 
 def case_anchored_c2(orc, scenes):
-    return _anchored_ticks(orc, scenes, scenes.config_scene("C2"), 1, "anchored C2", list(range(0, 64, 8)), 0.5)
+    # (one tick: the scored paths are the one-point initial ones, every cost ties and index 0 must win -- all 64 compared)
+    return _anchored_ticks(orc, scenes, scenes.config_scene("C2"), 1, "anchored C2", list(range(0, 64, 8)), 0.5,
+                           eval_agents="all")
 
 
 def case_anchored_c5_scene1(orc, scenes):
@@ -391,6 +395,9 @@ def test_oracle_anchored_rollouts(orc, scenes, name):
     st = _run_case(name, orc, scenes)
     assert st.walk.horizon >= 150, st.report()
     st.assert_ok(max_undecidable=ANCHORED_MAX_UNDECIDABLE, min_compared=10)
+    if name == "anchored_c2":
+        st.evaluation.assert_ok(0.0, min_compared=65)
+        assert st.evaluation.selections == 1, st.evaluation.report()
 
 
 # -- teeth: planners that are wrong in small ways must fail -----------------------------------------------------------
@@ -567,9 +574,9 @@ def test_ball_contains_fp64_velocity(policy, form):
 
 
 def test_new_shadow_modules_are_independent_of_the_oracle_and_the_package():
-    """hp_anchored.py and hp_shadow.py read planners only through the object handed to them: no import of oracle/, the
+    """hp_anchored.py, hp_shadow.py and hp_select.py read planners only through the object handed to them: no import of oracle/, the
     package, ctypes or torch"""
-    for name in ("hp_anchored.py", "hp_shadow.py"):
+    for name in ("hp_anchored.py", "hp_shadow.py", "hp_select.py"):
         tree = ast.parse(open(os.path.join(HERE, name)).read())
         mods = set()
         for node in ast.walk(tree):

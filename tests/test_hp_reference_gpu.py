@@ -222,12 +222,15 @@ ANCHORED_MAX_UNDECIDABLE = 0.02
 
 
 def _anchored(pmaf, scenes, scs, n_ticks, policy, name, agents, frac, lpa=0, expect=None, dynamic=False, walk_from=0,
-              host_coupling=False, mailbox=False):
+              host_coupling=False, mailbox=False, eval_agents=None):
     """n_ticks ticks of one handle holding the populations `scs`; from tick walk_from on, the sampled agents of every
     population are walked. host_coupling: C4 coupled on the host (shard.DualArmCoupling rows); mailbox: coupled inside the
-    handle through its peer mailbox, the shadow rebuilding the trailing rows"""
+    handle through its peer mailbox, the shadow rebuilding the trailing rows. eval_agents="all": every agent's cost and
+    the selected index are compared (hp_shadow.shadow_tick) in the first tick (one-point paths: the whole population
+    ties and index 0 must win) and in the last one (full-length paths)"""
     A = hp.Arith(policy)
     st = sh.Stats("%s [%s]" % (name, policy))
+    st.evaluation = sh.Stats("%s [%s], every cost and the selection" % (name, policy))   # (its own counts: st's cap is unchanged)
     single = len(scs) == 1
     starts = np.stack([s["start"] for s in scs])
     pl = pmaf.PmafPlanner(scs[0] if single else scs, device=0, mgr_init_pos=starts[0] if single else starts,
@@ -252,7 +255,8 @@ def _anchored(pmaf, scenes, scs, n_ticks, policy, name, agents, frac, lpa=0, exp
             rows = host.coupled_obstacles(pl.real_state()[0]) if host else obs
             ag = agents(pl) if callable(agents) else agents
             sh.shadow_tick(pl, scs[0] if single else scs, rows[0] if single else rows, ip, A, st,
-                           agents=ag if t >= walk_from else [], rollouts=ha.walker(frac, seed=t), coupling=coupling)
+                           agents=ag if t >= walk_from else [], rollouts=ha.walker(frac, seed=t), coupling=coupling,
+                           eval_agents=eval_agents if t in (0, n_ticks - 1) else None, eval_stats=st.evaluation)
             if dynamic:
                 obs = np.stack([scenes.advance_live_obstacles(o) for o in obs])
         if mailbox:
@@ -270,10 +274,17 @@ def _assert_anchored(st, min_horizon):
 
 @pytest.mark.parametrize("policy", ["xact", "fma", "fast"])
 def test_anchored_c2_w64_one_slot(pmaf, scenes, policy):
-    """BASELINE C2 (the bench headline: 64 agents, H = 200, 32 spheres) on k_rollout_w64, one obstacle slot per lane"""
+    """BASELINE C2 (the bench headline: 64 agents, H = 200, 32 spheres) on k_rollout_w64, one obstacle slot per lane.
+    Every agent's cost and the selected index are compared in the first and the last tick. Measured with the oracle in
+    the planner's place on one CPU core: 64 paths of 200 points cost 5.1 s per tick (99.0 s with all three ticks widened
+    against 88.8 s with the 8 walked agents' costs only), so one full-length tick is widened: + 5 s. C4 (10.7 s per arm
+    and tick for its 256 paths) and C5 stay sampled."""
     st = _anchored(pmaf, scenes, [scenes.config_scene("C2")], 3, policy, "anchored C2 w64 one-slot",
-                   _sample(64, 8), 0.15, expect=dict(lanes_per_agent=64, waves_per_agent=1, priority_slices=False))
+                   _sample(64, 8), 0.15, expect=dict(lanes_per_agent=64, waves_per_agent=1, priority_slices=False),
+                   eval_agents="all")
     _assert_anchored(st, 200)
+    st.evaluation.assert_ok(0.0, min_compared=2 * 65)
+    assert st.evaluation.selections == 2, st.evaluation.report()
 
 
 @pytest.mark.parametrize("policy", ["xact", "fma"])
