@@ -574,9 +574,9 @@ def test_ball_contains_fp64_velocity(policy, form):
 
 
 def test_new_shadow_modules_are_independent_of_the_oracle_and_the_package():
-    """hp_anchored.py, hp_shadow.py and hp_select.py read planners only through the object handed to them: no import of oracle/, the
-    package, ctypes or torch"""
-    for name in ("hp_anchored.py", "hp_shadow.py", "hp_select.py"):
+    """hp_anchored.py, hp_shadow.py, hp_select.py and hp_layout.py read planners only through the object handed to them: no
+    import of oracle/, the package, ctypes or torch"""
+    for name in ("hp_anchored.py", "hp_shadow.py", "hp_select.py", "hp_layout.py"):
         tree = ast.parse(open(os.path.join(HERE, name)).read())
         mods = set()
         for node in ast.walk(tree):
