@@ -67,8 +67,10 @@ struct CrossAudit {
   int n_agents = 0, n_other = 0;
   std::vector<double> clearance;  // [n_agents][n_other] least distance of the two paths, step by step, minus separation [m]
   std::vector<int> step;          // ... and the step at which it is reached (-1: an empty path, or nothing comparable)
+  std::vector<int> other_step;    // the overload with timing slack only: the OTHER path's step (step = this manager's)
   double at(int agent, int other) const { return clearance.at((size_t)agent * n_other + other); }
   int step_at(int agent, int other) const { return step.at((size_t)agent * n_other + other); }
+  int other_step_at(int agent, int other) const { return other_step.at((size_t)agent * n_other + other); }
 };
 
 class CfManager {
@@ -469,6 +471,20 @@ class CfManager {
   // ended path held at its last point (pmaf_cross_audit_tracks; no reference equivalent). separation = the sum of the
   // two bodies' radii. std::out_of_range for a path longer than max_prediction_steps or an empty list.
   CrossAudit crossAudit(const std::vector<std::vector<Vector3d>> &other_paths, const double separation) {
+    return crossAuditImpl(other_paths, separation, false, 0, 0);
+  }
+  // ... with timing slack: this arm may run up to `late` steps behind the other arm's clock, the other arm up to
+  // `other_late` behind this one's (pmaf_cross_audit_tracks_slack). step is this manager's step of the closest admitted
+  // pair of steps, other_step the other path's. std::out_of_range for a negative slack.
+  CrossAudit crossAudit(const std::vector<std::vector<Vector3d>> &other_paths, const double separation, const int late,
+                        const int other_late) {
+    if (late < 0 || other_late < 0) throw std::out_of_range("crossAudit: a slack must be >= 0");
+    return crossAuditImpl(other_paths, separation, true, late, other_late);
+  }
+
+ private:
+  CrossAudit crossAuditImpl(const std::vector<std::vector<Vector3d>> &other_paths, const double separation, const bool slack,
+                            const int late, const int other_late) {
     require();
     if (other_paths.empty()) throw std::out_of_range("crossAudit: no paths given");
     const size_t n = other_paths.size(), row = (size_t)cap_ * 3;
@@ -488,11 +504,21 @@ class CfManager {
     r.n_other = (int)n;
     r.clearance.resize((size_t)n_agents_ * n);
     std::vector<int32_t> st((size_t)n_agents_ * n);
-    check(pmaf_cross_audit_tracks(h_, 0, (int32_t)n, tracks.data(), len.data(), separation, r.clearance.data(), st.data()),
-          "crossAudit");
+    if (slack) {
+      std::vector<int32_t> so((size_t)n_agents_ * n);
+      check(pmaf_cross_audit_tracks_slack(h_, 0, (int32_t)n, tracks.data(), len.data(), separation, late, other_late,
+                                          r.clearance.data(), st.data(), so.data()),
+            "crossAudit");
+      r.other_step.assign(so.begin(), so.end());
+    } else {
+      check(pmaf_cross_audit_tracks(h_, 0, (int32_t)n, tracks.data(), len.data(), separation, r.clearance.data(), st.data()),
+            "crossAudit");
+    }
     r.step.assign(st.begin(), st.end());
     return r;
   }
+
+ public:
   // the whole planCallback sequence (B/src/panda_bimanual_control.cpp:336-352)
   // as one call: stop, evaluate, move the real agent one step, reset, start
   int planTick(const std::vector<Obstacle> &obstacles, const double delta_t, const double k_goal_dist,

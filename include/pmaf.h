@@ -355,6 +355,56 @@ int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, cons
 int pmaf_select_pair(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t *pair,
                      double *pair_cost, double *pair_clearance, int32_t *feasible);
 
+/* ---- cross audit with timing slack: arms that run late still keep apart (exports added under ABI 7) ----
+ * The cross audit above rests on "step k of both is one instant". On a robot that does not hold: the real end-effector
+ * trails its set-points (the closed-loop scenarios put a 30 % tracking lag in the loop), and the two arms' controllers
+ * do not trail by the same amount. A pair that is clear step against step can collide when one arm is three steps
+ * behind its schedule. These calls audit the same two path sets over a WINDOW of relative delays.
+ * Everything the block above defines carries over unchanged: path i of set A has the points x_0 .. x_{n-1}, path j of
+ * set B the points y_0 .. y_{m-1}; the hold rule xh_k = x_{min(k, n-1)}, yh_l = y_{min(l, m-1)} with K = max(n, m);
+ * dot in the build's association (pmaf_eval_order), every operation rounded, nothing fused.
+ * The slack is two non-negative step counts:
+ *   late_a:     A may be up to late_a steps behind B's clock: A stands at xh_k while B is already at yh_{k+s},
+ *               0 <= s <= late_a
+ *   late_b:     the same the other way round
+ *   admitted:   an index pair (k, l), 0 <= k, l < K, iff -late_b <= l - k <= late_a. Because of the hold rule this
+ *               window over [0, K)^2 covers every instant of every delay in range: a late arm waits at its point 0
+ *               before it starts, an ended arm waits at its last point.
+ *   d2(k, l)  = dot(xh_k - yh_l, xh_k - yh_l)
+ *   (step_a, step_b)(i,j) = the admitted pair that is smallest under the total order (d2, k, l): what a scan with k
+ *               ascending, then l ascending, and a strict `<` from +infinity finds. A NaN never wins; (-1, -1) when
+ *               nothing won.
+ *   clearance(i,j) = sqrt(d2(step_a, step_b)) - separation; +infinity when nothing won or a path is empty (n == 0 or
+ *               m == 0). No floor, no cap.
+ *   late_a < 0 or late_b < 0: PMAF_ERR_INVALID. Values >= max_prediction_steps mean every pair of steps (they are
+ *               clamped on the host before any device arithmetic: no index computation can overflow).
+ * Consequences:
+ *   - with (late_a, late_b) = (0, 0) the results equal pmaf_cross_audit's bit for bit, and step_a = step_b = step
+ *     (the calls below still run their own kernel then);
+ *   - the clearance never grows when either slack grows (the admitted set only gains pairs);
+ *   - audit(A, B, late_a, late_b) has the transposed clearance bits of audit(B, A, late_b, late_a): the admitted sets
+ *     are mirror images and d2 is symmetric bit for bit. The STEPS transpose only where the minimum is unique: the tie
+ *     rule is lexicographic in (k, l), A's step first, and the mirror image of its winner need not be the winner of
+ *     the mirrored scan (a minimum reached at (2, 5) and at (3, 4) is reported as (2, 5); the mirrored call sees it at
+ *     (5, 2) and (4, 3) and reports (4, 3), the mirror image of (3, 4)).
+ * Waiting, state and validation are those of the three calls above: the calls wait for the running rollout, change no
+ * planner state, and range-check population indices, track counts and inputs the same way.
+ *
+ * pmaf_cross_audit_slack: clearance [N][N], step_a / step_b [N][N], each NULL or given. */
+int pmaf_cross_audit_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, int32_t late_a, int32_t late_b,
+                           double *clearance, int32_t *step_a, int32_t *step_b);
+/* Set B from the caller, as pmaf_cross_audit_tracks: clearance [N][n_tracks], step_a / step_b likewise or NULL. */
+int pmaf_cross_audit_tracks_slack(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                                  const int32_t *n_track_points, double separation, int32_t late_a, int32_t late_b,
+                                  double *clearance, int32_t *step_a, int32_t *step_b);
+/* pmaf_select_pair's rule, exactly, on the slacked matrix (which stays on the device): feasible iff clearance >= margin,
+ * then the minimum of cost_a[i] + cost_b[j], else the greatest clearance, ties in row-major order. pair_steps [2] or
+ * NULL: (step_a, step_b) of the returned pair's matrix entry, (-1, -1) for the pair (-1, -1). The five-call tick:
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_pair_slack -> pmaf_move_real(agent_id = pair) -> pmaf_reset_agents -> pmaf_start */
+int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t late_a,
+                           int32_t late_b, int32_t *pair, double *pair_cost, double *pair_clearance, int32_t *feasible,
+                           int32_t *pair_steps);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

@@ -8,6 +8,9 @@
 #   pmaf_k_grp.hip   x3  the group rollout kernel (-DPMAF_GRP_MATH=0|2|3)
 #   pmaf_k_mw.hip    x3  the multi-wave-per-agent rollout kernel (62..256 obstacles at <= 1 wave per SIMD; -DPMAF_MW_MATH=1|2|3)
 #   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_cross_audit.hpp) ... + the launch interface
+#   pmaf_k_slack.hip     the cross audit with timing slack (k_cross_audit_slack), a unit of its own so that the other units'
+#                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
+#                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
 #   pmaf_shard.cpp       communicators + the winner-record exchange (RCCL / host-callback)
 # linked with -lamdhip64 -lrccl.
@@ -88,6 +91,7 @@ kcompile k_mw_m2 pmaf_k_mw.hip -DPMAF_MW_MATH=2
 kcompile k_mw_m1 pmaf_k_mw.hip -DPMAF_MW_MATH=1
 kcompile k_mw_m3 pmaf_k_mw.hip -DPMAF_MW_MATH=3 -ffp-contract=fast
 kcompile k_misc pmaf_k_misc.hip
+kcompile slack pmaf_k_slack.hip
 ( $CXX $HFLAGS -c pmaf_host.cpp -o "$OBJ/host.o" 2> "$OBJ/host.log" ) &
 pids+=($!); names+=("host")
 ( $CXX $HFLAGS -c pmaf_shard.cpp -o "$OBJ/shard.o" 2> "$OBJ/shard.log" ) &
@@ -100,8 +104,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o \
   "$OBJ"/host.o "$OBJ"/shard.o -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

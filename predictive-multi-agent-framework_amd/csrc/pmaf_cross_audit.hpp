@@ -69,6 +69,7 @@ __device__ __forceinline__ void xaudit_stage(double *s, const double *paths, con
   }
 }
 
+#ifndef PMAF_XAUDIT_NO_KERNELS   // pmaf_k_slack.hip shares the tile constants and xaudit_stage, not the kernels
 __global__ __launch_bounds__(PMAF_XAUDIT_THREADS) void k_cross_audit(CrossAuditArgs A) {
   constexpr int T = PMAF_XAUDIT_TILE, C = PMAF_XAUDIT_CHUNK, TP = T + 1;
   __shared__ double s_a[C * 3 * TP], s_b[C * 3 * TP];
@@ -204,5 +205,6 @@ __global__ __launch_bounds__(PMAF_XAUDIT_THREADS) void k_pair_final(PairArgs A, 
     *A.result = r;
   }
 }
+#endif  // PMAF_XAUDIT_NO_KERNELS
 
 }  // namespace pmaf

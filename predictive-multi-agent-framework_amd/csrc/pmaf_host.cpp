@@ -1548,20 +1548,23 @@ int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearan
 
 // ---- cross audit: two path sets against each other, step by step; the pair pick (include/pmaf.h) ----
 // Device scratch of one call: clearance [n_a][n_b] | partials | result | tracks [n_tracks][cap][3] | step [n_a][n_b] |
-// track lengths [n_tracks] (doubles first: every part stays 8-byte aligned)
+// track lengths [n_tracks] | the slacked calls' second step matrix [n_a][n_b] (doubles first, the int32 parts padded:
+// every part stays 8-byte aligned)
 struct XAuditBuf {
   double *clearance;
   PairBest *partial;
   PairResult *result;
   double *tracks;
   int32_t *step, *track_len;
+  int32_t *step_b;   // (the slacked calls only)
 };
-static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks) {
+static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps = false) {
   const size_t pairs = n_a * n_b;
   if (pairs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "cross audit: the number of pairs must stay below 2^31");
   const size_t b_clr = sizeof(double) * pairs, b_part = sizeof(PairBest) * PMAF_XAUDIT_PARTIALS, b_res = sizeof(PairResult);
   const size_t b_trk = sizeof(double) * n_tracks * (size_t)h->D.cap * 3, b_step = (sizeof(int32_t) * pairs + 7) & ~(size_t)7;
-  const size_t total = b_clr + b_part + b_res + b_trk + b_step + sizeof(int32_t) * n_tracks;
+  const size_t b_len = (sizeof(int32_t) * n_tracks + 7) & ~(size_t)7;
+  const size_t total = b_clr + b_part + b_res + b_trk + b_step + b_len + (two_steps ? b_step : 0);
   if (total > h->xaudit_bytes) {
     if (h->d_xaudit) { (void)hipFree(h->d_xaudit); h->d_xaudit = nullptr; }
     h->xaudit_bytes = 0;
@@ -1575,7 +1578,8 @@ static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t 
   B.result = reinterpret_cast<PairResult *>(p); p += b_res;
   B.tracks = reinterpret_cast<double *>(p); p += b_trk;
   B.step = reinterpret_cast<int32_t *>(p); p += b_step;
-  B.track_len = reinterpret_cast<int32_t *>(p);
+  B.track_len = reinterpret_cast<int32_t *>(p); p += b_len;
+  B.step_b = two_steps ? reinterpret_cast<int32_t *>(p) : nullptr;
   return B;
 }
 
@@ -1679,6 +1683,136 @@ int pmaf_select_pair(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separ
     *pair_cost = r.cost;
     *pair_clearance = r.clearance;
     *feasible = r.feasible;
+  });
+}
+
+// ---- cross audit with timing slack (include/pmaf.h): the same scratch, validation and waits; always k_cross_audit_slack ----
+// a slack of cap or more already admits every pair of steps: clamped here, before any device arithmetic
+static int32_t clamp_slack(const pmaf_planner *h, int32_t late, const char *who) {
+  if (late < 0) fail(PMAF_ERR_INVALID, std::string(who) + ": late_a and late_b must be >= 0");
+  return late < h->D.cap ? late : h->D.cap;
+}
+
+static XAuditBuf cross_audit_populations_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation,
+                                               int32_t late_a, int32_t late_b, bool want_a, bool want_b, const char *who) {
+  const DevView &D = h->D;
+  if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
+    fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
+  check_range(&separation, 1, "separation");
+  CrossAuditSlackArgs S{};
+  S.late_a = clamp_slack(h, late_a, who);
+  S.late_b = clamp_slack(h, late_b, who);
+  h->use_device();
+  sync(h);   // behind the running rollout, like the getters of its results
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, true);
+  CrossAuditArgs &A = S.X;
+  A.paths_a = D.paths + (size_t)pop_a * D.N * D.cap * 3;
+  A.paths_b = D.paths + (size_t)pop_b * D.N * D.cap * 3;
+  A.len_a = D.n_points + (size_t)pop_a * D.N;
+  A.len_b = D.n_points + (size_t)pop_b * D.N;
+  A.n_a = A.n_b = D.N;
+  A.cap = D.cap;
+  A.separation = separation;
+  A.clearance = B.clearance;
+  A.step = want_a ? B.step : nullptr;
+  S.step_b = want_b ? B.step_b : nullptr;
+  pmaf_k_launch_cross_audit_slack(S, h->stream);
+  HIP_CHECK(hipGetLastError());
+  return B;
+}
+
+int pmaf_cross_audit_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, int32_t late_a, int32_t late_b,
+                           double *clearance, int32_t *step_a, int32_t *step_b) {
+  return guarded([&] {
+    REQUIRE(h && clearance, "pmaf_cross_audit_slack: NULL argument");
+    const XAuditBuf B = cross_audit_populations_slack(h, pop_a, pop_b, separation, late_a, late_b, step_a != nullptr,
+                                                      step_b != nullptr, "pmaf_cross_audit_slack");
+    const size_t pairs = (size_t)h->D.N * h->D.N;
+    if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    h->download(clearance, B.clearance, pairs);
+  });
+}
+
+int pmaf_cross_audit_tracks_slack(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                                  const int32_t *n_track_points, double separation, int32_t late_a, int32_t late_b,
+                                  double *clearance, int32_t *step_a, int32_t *step_b) {
+  return guarded([&] {
+    REQUIRE(h && tracks && n_track_points && clearance, "pmaf_cross_audit_tracks_slack: NULL argument");
+    const DevView &D = h->D;
+    REQUIRE(pop >= 0 && pop < D.P, "pmaf_cross_audit_tracks_slack: population out of range");
+    REQUIRE(n_tracks > 0, "pmaf_cross_audit_tracks_slack: n_tracks must be > 0");
+    check_range(&separation, 1, "separation");
+    CrossAuditSlackArgs S{};
+    S.late_a = clamp_slack(h, late_a, "pmaf_cross_audit_tracks_slack");
+    S.late_b = clamp_slack(h, late_b, "pmaf_cross_audit_tracks_slack");
+    // rows past a track's count are neither checked nor copied
+    const size_t row = (size_t)D.cap * 3;
+    std::vector<double> packed((size_t)n_tracks * row, 0.0);
+    for (int32_t t = 0; t < n_tracks; t++) {
+      REQUIRE(n_track_points[t] >= 0 && n_track_points[t] <= D.cap, "pmaf_cross_audit_tracks_slack: a track's point count must be in [0, max_prediction_steps]");
+      check_range(tracks + t * row, (size_t)n_track_points[t] * 3, "tracks");
+      std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
+    }
+    h->use_device();
+    sync(h);
+    const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks, true);
+    HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
+    h->upload(B.tracks, packed.data(), packed.size());
+    CrossAuditArgs &A = S.X;
+    A.paths_a = D.paths + (size_t)pop * D.N * D.cap * 3;
+    A.paths_b = B.tracks;
+    A.len_a = D.n_points + (size_t)pop * D.N;
+    A.len_b = B.track_len;
+    A.n_a = D.N;
+    A.n_b = n_tracks;
+    A.cap = D.cap;
+    A.separation = separation;
+    A.clearance = B.clearance;
+    A.step = step_a ? B.step : nullptr;
+    S.step_b = step_b ? B.step_b : nullptr;
+    pmaf_k_launch_cross_audit_slack(S, h->stream);
+    HIP_CHECK(hipGetLastError());
+    const size_t pairs = (size_t)D.N * n_tracks;
+    if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+    h->download(clearance, B.clearance, pairs);
+  });
+}
+
+int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t late_a,
+                           int32_t late_b, int32_t *pair, double *pair_cost, double *pair_clearance, int32_t *feasible,
+                           int32_t *pair_steps) {
+  return guarded([&] {
+    REQUIRE(h && pair && pair_cost && pair_clearance && feasible, "pmaf_select_pair_slack: NULL argument");
+    check_range(&margin, 1, "margin");
+    const XAuditBuf B = cross_audit_populations_slack(h, pop_a, pop_b, separation, late_a, late_b, pair_steps != nullptr,
+                                                      pair_steps != nullptr, "pmaf_select_pair_slack");
+    const DevView &D = h->D;
+    PairArgs A{};   // pmaf_select_pair's reduction, as it is, over the slacked matrix
+    A.clearance = B.clearance;
+    A.cost_a = D.costs + (size_t)pop_a * D.N;
+    A.cost_b = D.costs + (size_t)pop_b * D.N;
+    A.n_a = A.n_b = D.N;
+    A.margin = margin;
+    A.partial = B.partial;
+    A.result = B.result;
+    pmaf_k_launch_pair_reduce(A, h->stream);
+    HIP_CHECK(hipGetLastError());
+    PairResult r{};
+    h->download(&r, B.result, 1);
+    pair[0] = r.i; pair[1] = r.j;
+    *pair_cost = r.cost;
+    *pair_clearance = r.clearance;
+    *feasible = r.feasible;
+    if (pair_steps) {   // the two steps of the returned pair's matrix entry
+      pair_steps[0] = pair_steps[1] = -1;
+      if (r.i >= 0 && r.j >= 0) {
+        const size_t o = (size_t)r.i * D.N + r.j;
+        h->download(pair_steps, B.step + o, 1);
+        h->download(pair_steps + 1, B.step_b + o, 1);
+      }
+    }
   });
 }
 

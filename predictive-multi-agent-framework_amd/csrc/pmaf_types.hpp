@@ -198,6 +198,12 @@ struct CrossAuditArgs {
   double *clearance;                 // [n_a][n_b]
   int32_t *step;                     // [n_a][n_b] or NULL
 };
+// cross audit with timing slack (pmaf_cross_audit_slack / ..._tracks_slack / pmaf_select_pair_slack): pmaf_k_slack.hip
+struct CrossAuditSlackArgs {
+  CrossAuditArgs X;                  // the two sets, separation and clearance as above; X.step = step_a [n_a][n_b] or NULL
+  int32_t *step_b;                   // [n_a][n_b] or NULL
+  int late_a, late_b;                // 0 .. cap each (clamped on the host): admitted (k, l) iff -late_b <= l - k <= late_a
+};
 // running results of the pair reduction: the cheapest feasible sum and the greatest clearance, each with its row-major
 // index (0x7fffffff: nothing won). The clearance is carried NEGATED so that both are minima under (value, index).
 struct PairBest {
@@ -219,7 +225,7 @@ struct PairArgs {
 };
 
 // ---------------------------------------------------------------------------
-// launch interface: implemented in pmaf_k_w64.hip / pmaf_k_grp.hip / pmaf_k_misc.hip
+// launch interface: implemented in pmaf_k_w64.hip / pmaf_k_grp.hip / pmaf_k_misc.hip / pmaf_k_slack.hip
 // ---------------------------------------------------------------------------
 // k_rollout_w64<TILES, MATH, DPPSUM, PLAIN> on grid (N, P); tiles in {1,2,4}; plain: every k_attr != 0 and unit mass
 // (the step without those two cases, pmaf_k_w64.hip); dppsum: the ordered force sum by the DPP
@@ -260,6 +266,8 @@ void pmaf_k_launch_eval_obstacle_distance(const DevView &D, const double *obs, d
 void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *track, hipStream_t s);
 // k_cross_audit on a grid of (n_b, n_a) / 32 tiles
 void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s);
+// k_cross_audit_slack on the same grid (pmaf_k_slack.hip)
+void pmaf_k_launch_cross_audit_slack(const CrossAuditSlackArgs &A, hipStream_t s);
 // the two stages of the pair reduction back to back
 void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s);
 // opt the kernels that take dynamic LDS into more than the 64 KB default

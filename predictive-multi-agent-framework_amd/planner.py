@@ -68,6 +68,9 @@ SYMBOLS = {
     "pmaf_cross_audit": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, _dp, _ip]),
     "pmaf_cross_audit_tracks": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, _dp, _ip]),
     "pmaf_select_pair": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_double, _ip, _dp, _dp, _ip]),
+    "pmaf_cross_audit_slack": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip]),
+    "pmaf_cross_audit_tracks_slack": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip]),
+    "pmaf_select_pair_slack": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -375,6 +378,38 @@ class PmafPlanner:
         self._chk(self.L.pmaf_select_pair(self._h, int(pop_a), int(pop_b), float(separation), float(margin), _pi(pair),
                                           C.byref(cost), C.byref(clr), C.byref(feas)))
         return {"pair": (int(pair[0]), int(pair[1])), "cost": cost.value, "clearance": clr.value, "feasible": bool(feas.value)}
+
+    # -- cross audit with timing slack: A up to late_a steps behind B's clock, B up to late_b behind A's --
+    def cross_audit_slack(self, pop_a, pop_b, separation, late_a, late_b, steps=False):
+        """clearance [N][N] of pop_a's current paths against pop_b's over every admitted pair of steps
+        (pmaf_cross_audit_slack); with steps=True (clearance, step_a, step_b), the steps int32 [N][N]"""
+        clr = np.zeros((self.N, self.N))
+        sa = np.zeros((self.N, self.N), dtype=np.int32) if steps else None
+        sb = np.zeros((self.N, self.N), dtype=np.int32) if steps else None
+        self._chk(self.L.pmaf_cross_audit_slack(self._h, int(pop_a), int(pop_b), float(separation), int(late_a), int(late_b),
+                                                _p(clr), _pi(sa), _pi(sb)))
+        return (clr, sa, sb) if steps else clr
+
+    def cross_audit_tracks_slack(self, pop, tracks, n_track_points, separation, late_a, late_b, steps=False):
+        """population pop's current paths against the caller's tracks [n_tracks][cap][3] (pmaf_cross_audit_tracks_slack):
+        clearance [N][n_tracks], with steps=True (clearance, step_a, step_b)"""
+        n = np.ascontiguousarray(n_track_points, dtype=np.int32).reshape(-1)
+        tr = _d(tracks).reshape(n.size, self.cap, 3)
+        clr = np.zeros((self.N, n.size))
+        sa = np.zeros((self.N, n.size), dtype=np.int32) if steps else None
+        sb = np.zeros((self.N, n.size), dtype=np.int32) if steps else None
+        self._chk(self.L.pmaf_cross_audit_tracks_slack(self._h, int(pop), n.size, _p(tr), _pi(n), float(separation),
+                                                       int(late_a), int(late_b), _p(clr), _pi(sa), _pi(sb)))
+        return (clr, sa, sb) if steps else clr
+
+    def select_pair_slack(self, pop_a, pop_b, separation, margin, late_a, late_b):
+        """select_pair on the slacked matrix (pmaf_select_pair_slack): its dict plus steps (step_a, step_b) of the pair"""
+        pair, st = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        cost, clr, feas = C.c_double(0), C.c_double(0), C.c_int32(0)
+        self._chk(self.L.pmaf_select_pair_slack(self._h, int(pop_a), int(pop_b), float(separation), float(margin), int(late_a),
+                                                int(late_b), _pi(pair), C.byref(cost), C.byref(clr), C.byref(feas), _pi(st)))
+        return {"pair": (int(pair[0]), int(pair[1])), "cost": cost.value, "clearance": clr.value, "feasible": bool(feas.value),
+                "steps": (int(st[0]), int(st[1]))}
 
     def link_force(self, link_pos, k_r_force, obstacles, pop=0):
         lp, k, o = _d(link_pos), _d(k_r_force), self._obs(obstacles)
