@@ -7,8 +7,9 @@
 #                        contracted one, the only units compiled with -ffp-contract=fast)
 #   pmaf_k_grp.hip   x3  the group rollout kernel (-DPMAF_GRP_MATH=0|2|3)
 #   pmaf_k_mw.hip    x3  the multi-wave-per-agent rollout kernel (62..256 obstacles at <= 1 wave per SIMD; -DPMAF_MW_MATH=1|2|3)
-#   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_cross_audit.hpp) ... + the launch interface
-#   pmaf_k_slack.hip     the cross audit with timing slack (k_cross_audit_slack), a unit of its own so that the other units'
+#   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_xaudit_kernels.hpp) ... + the launch interface
+#   pmaf_k_slack.hip     the cross audit with timing slack (k_cross_audit_slack; it shares the tile header
+#                        pmaf_cross_audit.hpp with the cross audit), a unit of its own so that the other units'
 #                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
 #                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
@@ -50,7 +51,7 @@ KFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-m
 # PMAF_EXTRA_HFLAGS / PMAF_EXTRA_LDFLAGS: host objects / link line only (sanitizer builds: tools/asan.sh)
 HFLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -D__HIP_PLATFORM_AMD__ -I$ROCM/include ${PMAF_EXTRA_FLAGS} ${PMAF_EXTRA_HFLAGS}"
 
-DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_cross_audit.hpp"
+DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp"
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
 FLAGS_CHANGED=0

@@ -1546,7 +1546,14 @@ int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearan
   });
 }
 
-// ---- cross audit: two path sets against each other, step by step; the pair pick (include/pmaf.h) ----
+// ---- cross audit: two path sets against each other; the pair pick (include/pmaf.h, "cross audit" and "cross audit with
+// timing slack"). Six calls, one path: a call is "population against population" or "population against uploaded
+// tracks", step against step (k_cross_audit) or slacked (k_cross_audit_slack), and a select call adds the pair pick ----
+// a slacked call's two slacks. A null pointer is the step-against-step audit; a slack of (0, 0) is a slacked call like
+// any other and runs k_cross_audit_slack.
+struct XAuditSlack {
+  int32_t late_a, late_b;
+};
 // Device scratch of one call: clearance [n_a][n_b] | partials | result | tracks [n_tracks][cap][3] | step [n_a][n_b] |
 // track lengths [n_tracks] | the slacked calls' second step matrix [n_a][n_b] (doubles first, the int32 parts padded:
 // every part stays 8-byte aligned)
@@ -1558,7 +1565,7 @@ struct XAuditBuf {
   int32_t *step, *track_len;
   int32_t *step_b;   // (the slacked calls only)
 };
-static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps = false) {
+static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps) {
   const size_t pairs = n_a * n_b;
   if (pairs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "cross audit: the number of pairs must stay below 2^31");
   const size_t b_clr = sizeof(double) * pairs, b_part = sizeof(PairBest) * PMAF_XAUDIT_PARTIALS, b_res = sizeof(PairResult);
@@ -1583,38 +1590,123 @@ static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t 
   return B;
 }
 
+// host-side validation of a slacked call's slacks, before any wait. A slack of cap or more already admits every pair of
+// steps: clamped here, before any device arithmetic.
+static void clamp_slack(const pmaf_planner *h, XAuditSlack *slack, const char *who) {
+  if (!slack) return;
+  for (int32_t *late : {&slack->late_a, &slack->late_b}) {
+    if (*late < 0) fail(PMAF_ERR_INVALID, std::string(who) + ": late_a and late_b must be >= 0");
+    *late = *late < h->D.cap ? *late : h->D.cap;
+  }
+}
+
+// the launch: set A against set B into the scratch, the step matrices where they are wanted
+static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *paths_a, const int32_t *len_a, int32_t n_a,
+                          const double *paths_b, const int32_t *len_b, int32_t n_b, double separation,
+                          const XAuditSlack *slack, bool want_a, bool want_b) {
+  CrossAuditSlackArgs S{};
+  CrossAuditArgs &A = S.X;
+  A.paths_a = paths_a;
+  A.paths_b = paths_b;
+  A.len_a = len_a;
+  A.len_b = len_b;
+  A.n_a = n_a;
+  A.n_b = n_b;
+  A.cap = h->D.cap;
+  A.separation = separation;
+  A.clearance = B.clearance;
+  A.step = want_a ? B.step : nullptr;
+  if (slack) {
+    S.late_a = slack->late_a;
+    S.late_b = slack->late_b;
+    S.step_b = want_b ? B.step_b : nullptr;
+    pmaf_k_launch_cross_audit_slack(S, h->stream);
+  } else {
+    pmaf_k_launch_cross_audit(A, h->stream);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// the matrix (and the step matrices the caller asked for) back to the host
+static void xaudit_download(pmaf_planner *h, const XAuditBuf &B, size_t pairs, double *clearance, int32_t *step_a,
+                            int32_t *step_b) {
+  if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+  if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
+  h->download(clearance, B.clearance, pairs);
+}
+
 // population pop_a's paths against population pop_b's where they lie; the matrix stays in the scratch
-static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, bool want_step,
-                                         const char *who) {
+static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, XAuditSlack *slack,
+                                         bool want_a, bool want_b, const char *who) {
   const DevView &D = h->D;
   if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
     fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
   check_range(&separation, 1, "separation");
+  clamp_slack(h, slack, who);
   h->use_device();
   sync(h);   // behind the running rollout, like the getters of its results
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0);
-  CrossAuditArgs A{};
-  A.paths_a = D.paths + (size_t)pop_a * D.N * D.cap * 3;
-  A.paths_b = D.paths + (size_t)pop_b * D.N * D.cap * 3;
-  A.len_a = D.n_points + (size_t)pop_a * D.N;
-  A.len_b = D.n_points + (size_t)pop_b * D.N;
-  A.n_a = A.n_b = D.N;
-  A.cap = D.cap;
-  A.separation = separation;
-  A.clearance = B.clearance;
-  A.step = want_step ? B.step : nullptr;
-  pmaf_k_launch_cross_audit(A, h->stream);
-  HIP_CHECK(hipGetLastError());
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr);
+  xaudit_launch(h, B, D.paths + (size_t)pop_a * D.N * D.cap * 3, D.n_points + (size_t)pop_a * D.N, D.N,
+                D.paths + (size_t)pop_b * D.N * D.cap * 3, D.n_points + (size_t)pop_b * D.N, D.N, separation, slack, want_a,
+                want_b);
   return B;
+}
+
+// population pop's paths against the caller's tracks, uploaded into the scratch; the results back to the host
+static void cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                               const int32_t *n_track_points, double separation, XAuditSlack *slack, double *clearance,
+                               int32_t *step_a, int32_t *step_b, const char *who) {
+  const DevView &D = h->D;
+  REQUIRE(pop >= 0 && pop < D.P, std::string(who) + ": population out of range");
+  REQUIRE(n_tracks > 0, std::string(who) + ": n_tracks must be > 0");
+  check_range(&separation, 1, "separation");
+  clamp_slack(h, slack, who);
+  // rows past a track's count are neither checked nor copied
+  const size_t row = (size_t)D.cap * 3;
+  std::vector<double> packed((size_t)n_tracks * row, 0.0);
+  for (int32_t t = 0; t < n_tracks; t++) {
+    REQUIRE(n_track_points[t] >= 0 && n_track_points[t] <= D.cap, std::string(who) + ": a track's point count must be in [0, max_prediction_steps]");
+    check_range(tracks + t * row, (size_t)n_track_points[t] * 3, "tracks");
+    std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
+  }
+  h->use_device();
+  sync(h);
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks, slack != nullptr);
+  HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
+  h->upload(B.tracks, packed.data(), packed.size());
+  xaudit_launch(h, B, D.paths + (size_t)pop * D.N * D.cap * 3, D.n_points + (size_t)pop * D.N, D.N, B.tracks, B.track_len,
+                n_tracks, separation, slack, step_a != nullptr, step_b != nullptr);
+  xaudit_download(h, B, (size_t)D.N * n_tracks, clearance, step_a, step_b);
+}
+
+// the pair pick over the matrix cross_audit_populations left in the scratch. The costs are read where pmaf_get_costs
+// reads them (DevView::costs, behind the same wait), so both calls see the same values in every state of the handle.
+static void select_pair(pmaf_planner *h, const XAuditBuf &B, int32_t pop_a, int32_t pop_b, double margin, int32_t *pair,
+                        double *pair_cost, double *pair_clearance, int32_t *feasible) {
+  const DevView &D = h->D;
+  PairArgs A{};
+  A.clearance = B.clearance;
+  A.cost_a = D.costs + (size_t)pop_a * D.N;
+  A.cost_b = D.costs + (size_t)pop_b * D.N;
+  A.n_a = A.n_b = D.N;
+  A.margin = margin;
+  A.partial = B.partial;
+  A.result = B.result;
+  pmaf_k_launch_pair_reduce(A, h->stream);
+  HIP_CHECK(hipGetLastError());
+  PairResult r{};
+  h->download(&r, B.result, 1);
+  pair[0] = r.i; pair[1] = r.j;
+  *pair_cost = r.cost;
+  *pair_clearance = r.clearance;
+  *feasible = r.feasible;
 }
 
 int pmaf_cross_audit(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double *clearance, int32_t *step) {
   return guarded([&] {
     REQUIRE(h && clearance, "pmaf_cross_audit: NULL argument");
-    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, step != nullptr, "pmaf_cross_audit");
-    const size_t pairs = (size_t)h->D.N * h->D.N;
-    if (step) HIP_CHECK(hipMemcpyAsync(step, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    h->download(clearance, B.clearance, pairs);
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, step != nullptr, false, "pmaf_cross_audit");
+    xaudit_download(h, B, (size_t)h->D.N * h->D.N, clearance, step, nullptr);
   });
 }
 
@@ -1622,39 +1714,8 @@ int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, cons
                             const int32_t *n_track_points, double separation, double *clearance, int32_t *step) {
   return guarded([&] {
     REQUIRE(h && tracks && n_track_points && clearance, "pmaf_cross_audit_tracks: NULL argument");
-    const DevView &D = h->D;
-    REQUIRE(pop >= 0 && pop < D.P, "pmaf_cross_audit_tracks: population out of range");
-    REQUIRE(n_tracks > 0, "pmaf_cross_audit_tracks: n_tracks must be > 0");
-    check_range(&separation, 1, "separation");
-    // rows past a track's count are neither checked nor copied
-    const size_t row = (size_t)D.cap * 3;
-    std::vector<double> packed((size_t)n_tracks * row, 0.0);
-    for (int32_t t = 0; t < n_tracks; t++) {
-      REQUIRE(n_track_points[t] >= 0 && n_track_points[t] <= D.cap, "pmaf_cross_audit_tracks: a track's point count must be in [0, max_prediction_steps]");
-      check_range(tracks + t * row, (size_t)n_track_points[t] * 3, "tracks");
-      std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
-    }
-    h->use_device();
-    sync(h);
-    const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks);
-    HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
-    h->upload(B.tracks, packed.data(), packed.size());
-    CrossAuditArgs A{};
-    A.paths_a = D.paths + (size_t)pop * D.N * D.cap * 3;
-    A.paths_b = B.tracks;
-    A.len_a = D.n_points + (size_t)pop * D.N;
-    A.len_b = B.track_len;
-    A.n_a = D.N;
-    A.n_b = n_tracks;
-    A.cap = D.cap;
-    A.separation = separation;
-    A.clearance = B.clearance;
-    A.step = step ? B.step : nullptr;
-    pmaf_k_launch_cross_audit(A, h->stream);
-    HIP_CHECK(hipGetLastError());
-    const size_t pairs = (size_t)D.N * n_tracks;
-    if (step) HIP_CHECK(hipMemcpyAsync(step, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    h->download(clearance, B.clearance, pairs);
+    cross_audit_tracks(h, pop, n_tracks, tracks, n_track_points, separation, nullptr, clearance, step, nullptr,
+                       "pmaf_cross_audit_tracks");
   });
 }
 
@@ -1663,74 +1724,19 @@ int pmaf_select_pair(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separ
   return guarded([&] {
     REQUIRE(h && pair && pair_cost && pair_clearance && feasible, "pmaf_select_pair: NULL argument");
     check_range(&margin, 1, "margin");
-    // the costs are read where pmaf_get_costs reads them (DevView::costs, behind the same wait), so both calls see the
-    // same values in every state of the handle
-    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, false, "pmaf_select_pair");
-    const DevView &D = h->D;
-    PairArgs A{};
-    A.clearance = B.clearance;
-    A.cost_a = D.costs + (size_t)pop_a * D.N;
-    A.cost_b = D.costs + (size_t)pop_b * D.N;
-    A.n_a = A.n_b = D.N;
-    A.margin = margin;
-    A.partial = B.partial;
-    A.result = B.result;
-    pmaf_k_launch_pair_reduce(A, h->stream);
-    HIP_CHECK(hipGetLastError());
-    PairResult r{};
-    h->download(&r, B.result, 1);
-    pair[0] = r.i; pair[1] = r.j;
-    *pair_cost = r.cost;
-    *pair_clearance = r.clearance;
-    *feasible = r.feasible;
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, false, false, "pmaf_select_pair");
+    select_pair(h, B, pop_a, pop_b, margin, pair, pair_cost, pair_clearance, feasible);
   });
-}
-
-// ---- cross audit with timing slack (include/pmaf.h): the same scratch, validation and waits; always k_cross_audit_slack ----
-// a slack of cap or more already admits every pair of steps: clamped here, before any device arithmetic
-static int32_t clamp_slack(const pmaf_planner *h, int32_t late, const char *who) {
-  if (late < 0) fail(PMAF_ERR_INVALID, std::string(who) + ": late_a and late_b must be >= 0");
-  return late < h->D.cap ? late : h->D.cap;
-}
-
-static XAuditBuf cross_audit_populations_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation,
-                                               int32_t late_a, int32_t late_b, bool want_a, bool want_b, const char *who) {
-  const DevView &D = h->D;
-  if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
-    fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
-  check_range(&separation, 1, "separation");
-  CrossAuditSlackArgs S{};
-  S.late_a = clamp_slack(h, late_a, who);
-  S.late_b = clamp_slack(h, late_b, who);
-  h->use_device();
-  sync(h);   // behind the running rollout, like the getters of its results
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, true);
-  CrossAuditArgs &A = S.X;
-  A.paths_a = D.paths + (size_t)pop_a * D.N * D.cap * 3;
-  A.paths_b = D.paths + (size_t)pop_b * D.N * D.cap * 3;
-  A.len_a = D.n_points + (size_t)pop_a * D.N;
-  A.len_b = D.n_points + (size_t)pop_b * D.N;
-  A.n_a = A.n_b = D.N;
-  A.cap = D.cap;
-  A.separation = separation;
-  A.clearance = B.clearance;
-  A.step = want_a ? B.step : nullptr;
-  S.step_b = want_b ? B.step_b : nullptr;
-  pmaf_k_launch_cross_audit_slack(S, h->stream);
-  HIP_CHECK(hipGetLastError());
-  return B;
 }
 
 int pmaf_cross_audit_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, int32_t late_a, int32_t late_b,
                            double *clearance, int32_t *step_a, int32_t *step_b) {
   return guarded([&] {
     REQUIRE(h && clearance, "pmaf_cross_audit_slack: NULL argument");
-    const XAuditBuf B = cross_audit_populations_slack(h, pop_a, pop_b, separation, late_a, late_b, step_a != nullptr,
-                                                      step_b != nullptr, "pmaf_cross_audit_slack");
-    const size_t pairs = (size_t)h->D.N * h->D.N;
-    if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    h->download(clearance, B.clearance, pairs);
+    XAuditSlack slack{late_a, late_b};
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, &slack, step_a != nullptr, step_b != nullptr,
+                                                "pmaf_cross_audit_slack");
+    xaudit_download(h, B, (size_t)h->D.N * h->D.N, clearance, step_a, step_b);
   });
 }
 
@@ -1739,44 +1745,9 @@ int pmaf_cross_audit_tracks_slack(pmaf_planner *h, int32_t pop, int32_t n_tracks
                                   double *clearance, int32_t *step_a, int32_t *step_b) {
   return guarded([&] {
     REQUIRE(h && tracks && n_track_points && clearance, "pmaf_cross_audit_tracks_slack: NULL argument");
-    const DevView &D = h->D;
-    REQUIRE(pop >= 0 && pop < D.P, "pmaf_cross_audit_tracks_slack: population out of range");
-    REQUIRE(n_tracks > 0, "pmaf_cross_audit_tracks_slack: n_tracks must be > 0");
-    check_range(&separation, 1, "separation");
-    CrossAuditSlackArgs S{};
-    S.late_a = clamp_slack(h, late_a, "pmaf_cross_audit_tracks_slack");
-    S.late_b = clamp_slack(h, late_b, "pmaf_cross_audit_tracks_slack");
-    // rows past a track's count are neither checked nor copied
-    const size_t row = (size_t)D.cap * 3;
-    std::vector<double> packed((size_t)n_tracks * row, 0.0);
-    for (int32_t t = 0; t < n_tracks; t++) {
-      REQUIRE(n_track_points[t] >= 0 && n_track_points[t] <= D.cap, "pmaf_cross_audit_tracks_slack: a track's point count must be in [0, max_prediction_steps]");
-      check_range(tracks + t * row, (size_t)n_track_points[t] * 3, "tracks");
-      std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
-    }
-    h->use_device();
-    sync(h);
-    const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks, true);
-    HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
-    h->upload(B.tracks, packed.data(), packed.size());
-    CrossAuditArgs &A = S.X;
-    A.paths_a = D.paths + (size_t)pop * D.N * D.cap * 3;
-    A.paths_b = B.tracks;
-    A.len_a = D.n_points + (size_t)pop * D.N;
-    A.len_b = B.track_len;
-    A.n_a = D.N;
-    A.n_b = n_tracks;
-    A.cap = D.cap;
-    A.separation = separation;
-    A.clearance = B.clearance;
-    A.step = step_a ? B.step : nullptr;
-    S.step_b = step_b ? B.step_b : nullptr;
-    pmaf_k_launch_cross_audit_slack(S, h->stream);
-    HIP_CHECK(hipGetLastError());
-    const size_t pairs = (size_t)D.N * n_tracks;
-    if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
-    h->download(clearance, B.clearance, pairs);
+    XAuditSlack slack{late_a, late_b};
+    cross_audit_tracks(h, pop, n_tracks, tracks, n_track_points, separation, &slack, clearance, step_a, step_b,
+                       "pmaf_cross_audit_tracks_slack");
   });
 }
 
@@ -1786,29 +1757,14 @@ int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double
   return guarded([&] {
     REQUIRE(h && pair && pair_cost && pair_clearance && feasible, "pmaf_select_pair_slack: NULL argument");
     check_range(&margin, 1, "margin");
-    const XAuditBuf B = cross_audit_populations_slack(h, pop_a, pop_b, separation, late_a, late_b, pair_steps != nullptr,
-                                                      pair_steps != nullptr, "pmaf_select_pair_slack");
-    const DevView &D = h->D;
-    PairArgs A{};   // pmaf_select_pair's reduction, as it is, over the slacked matrix
-    A.clearance = B.clearance;
-    A.cost_a = D.costs + (size_t)pop_a * D.N;
-    A.cost_b = D.costs + (size_t)pop_b * D.N;
-    A.n_a = A.n_b = D.N;
-    A.margin = margin;
-    A.partial = B.partial;
-    A.result = B.result;
-    pmaf_k_launch_pair_reduce(A, h->stream);
-    HIP_CHECK(hipGetLastError());
-    PairResult r{};
-    h->download(&r, B.result, 1);
-    pair[0] = r.i; pair[1] = r.j;
-    *pair_cost = r.cost;
-    *pair_clearance = r.clearance;
-    *feasible = r.feasible;
+    XAuditSlack slack{late_a, late_b};
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, &slack, pair_steps != nullptr,
+                                                pair_steps != nullptr, "pmaf_select_pair_slack");
+    select_pair(h, B, pop_a, pop_b, margin, pair, pair_cost, pair_clearance, feasible);
     if (pair_steps) {   // the two steps of the returned pair's matrix entry
       pair_steps[0] = pair_steps[1] = -1;
-      if (r.i >= 0 && r.j >= 0) {
-        const size_t o = (size_t)r.i * D.N + r.j;
+      if (pair[0] >= 0 && pair[1] >= 0) {
+        const size_t o = (size_t)pair[0] * h->D.N + pair[1];
         h->download(pair_steps, B.step + o, 1);
         h->download(pair_steps + 1, B.step_b + o, 1);
       }

@@ -8,7 +8,7 @@
 //   k_link_force    CfAgent::bodyForce (B/src/cf_agent.cpp:229-234).
 //   k_winner        packs winner records for sharded runs.
 //   k_audit_track, k_path_audit (pmaf_path_audit.hpp)  the predicted paths against a live obstacle list.
-//   k_cross_audit, k_pair_reduce, k_pair_final (pmaf_cross_audit.hpp)  two path sets against each other, the pair pick.
+//   k_cross_audit, k_pair_reduce, k_pair_final (pmaf_xaudit_kernels.hpp)  two path sets against each other, the pair pick.
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -18,7 +18,7 @@
 #include "pmaf_rollout_w64.hpp"
 #include "pmaf_rollout_grp.hpp"
 #include "pmaf_path_audit.hpp"
-#include "pmaf_cross_audit.hpp"
+#include "pmaf_xaudit_kernels.hpp"
 
 using namespace pmaf;
 

@@ -12,12 +12,10 @@
 //   clearance         = sqrt(d2(step_a, step_b)) - separation   (+inf when nothing won or a path is empty)
 //
 // k_cross_audit_slack   N_a * N_b * K * (late_a + late_b + 1) independent pair-steps, a band around the diagonal of
-//                 every pair's K x K table. Ownership is k_cross_audit's: a block of 256 threads owns T x T = 32 x 32
-//                 paths, thread (ty, tx) = (tid / 16, tid % 16) keeps the 2 x 2 pairs (ty + 16 r, tx + 16 c) with one
-//                 running (d2, k, l) each, a pair belongs to one thread: no reduction across threads, no atomics, and a
-//                 result that does not depend on the tiling.
-//                  - LDS does not depend on the slack: one chunk of C = 16 steps of A and one of B in xaudit_stage's
-//                    padded SoA layout (24.8 KB per block, as in k_cross_audit). For every chunk [k0, k0 + C) of A the
+//                 every pair's K x K table. Ownership, LDS layout and staging are the tile's (pmaf_cross_audit.hpp, shared
+//                 with k_cross_audit); a thread keeps one running (d2, k, l) for each of its 2 x 2 pairs.
+//                  - LDS does not depend on the slack: one chunk of C = 16 steps of A and one of B in the tile's layout
+//                    (24.8 KB per block, as in k_cross_audit). For every chunk [k0, k0 + C) of A the
 //                    block walks the chunks of B, on the same grid of multiples of C, that meet the band
 //                    [k0 - late_b, k0 + C - 1 + late_a] clipped to [0, K): A's chunk is staged once, B's once per
 //                    chunk pair (6 global loads per thread against up to 4 C^2 = 1024 pair-steps).
@@ -45,13 +43,11 @@
 //                    late_a and l - k' > l - k >= -late_b; only l clipped the mirror image. And (k', l') < (k, l). So
 //                    every such step ties with (or, NaN, loses like) an ADMITTED step of a smaller (k, l) that the
 //                    block also visits, and the order above never prefers it.
-//                  - empty paths stage their row 0 and are overwritten with +inf / -1 / -1 at the end, as in
-//                    k_cross_audit; paths past the ragged edge of N_a / N_b are computed and not stored.
+//                  - empty paths and the ragged edge of N_a / N_b: the tile's rule (xaudit_store_pair: +inf / -1 / -1).
 #include <hip/hip_runtime.h>
 
 #include "pmaf_types.hpp"
 #include "pmaf_device.hpp"
-#define PMAF_XAUDIT_NO_KERNELS
 #include "pmaf_cross_audit.hpp"
 
 using namespace pmaf;
@@ -86,27 +82,7 @@ __global__ __launch_bounds__(PMAF_XAUDIT_THREADS) void k_cross_audit_slack(Cross
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int a0 = blockIdx.y * T, b0 = blockIdx.x * T;
   const int late_a = S.late_a, late_b = S.late_b;
-  if (tid < 2 * T) {   // wave 0: the tile's path lengths and the longest of them
-    const int t = tid & (T - 1);
-    const bool is_b = tid >= T;
-    int p = (is_b ? b0 : a0) + t;
-    const int count = is_b ? A.n_b : A.n_a;
-    p = p < count ? p : count - 1;
-    int n = (is_b ? A.len_b : A.len_a)[p];
-    PMAF_BOUND(n >= 0 && n <= A.cap);
-    n = n < A.cap ? n : A.cap;
-    n = n > 0 ? n : 0;
-    (is_b ? s_nb : s_na)[t] = n;
-    int m = n;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(m, off);
-      m = o > m ? o : m;
-    }
-    if (tid == 0) s_k[0] = m;
-  }
-  __syncthreads();
-  const int K = s_k[0];
+  const int K = xaudit_tile_lengths(A, a0, b0, s_na, s_nb, s_k);
   PMAF_BOUND(late_a >= 0 && late_a <= A.cap && late_b >= 0 && late_b <= A.cap);
   const double inf = __builtin_huge_val();
   double best[2][2] = {{inf, inf}, {inf, inf}};
@@ -148,17 +124,8 @@ __global__ __launch_bounds__(PMAF_XAUDIT_THREADS) void k_cross_audit_slack(Cross
 #pragma unroll
   for (int r = 0; r < 2; r++)
 #pragma unroll
-    for (int c = 0; c < 2; c++) {
-      const int ti = ty + 16 * r, tj = tx + 16 * c;
-      const int i = a0 + ti, j = b0 + tj;
-      if (i < A.n_a && j < A.n_b) {
-        const bool won = bk[r][c] >= 0 && s_na[ti] > 0 && s_nb[tj] > 0;
-        const size_t o = (size_t)i * A.n_b + j;
-        A.clearance[o] = won ? __builtin_sqrt(best[r][c]) - A.separation : inf;
-        if (A.step) A.step[o] = won ? bk[r][c] : -1;
-        if (S.step_b) S.step_b[o] = won ? bl[r][c] : -1;
-      }
-    }
+    for (int c = 0; c < 2; c++)
+      xaudit_store_pair(A, a0, b0, ty + 16 * r, tx + 16 * c, s_na, s_nb, best[r][c], bk[r][c], bl[r][c], S.step_b);
 }
 
 void pmaf_k_launch_cross_audit_slack(const CrossAuditSlackArgs &A, hipStream_t s) {

@@ -360,11 +360,15 @@ class PmafPlanner:
         self._chk(self.L.pmaf_cross_audit(self._h, int(pop_a), int(pop_b), float(separation), _p(clr), _pi(st)))
         return (clr, st) if step else clr
 
+    def _tracks(self, tracks, n_track_points):
+        """the caller's tracks as the two track calls take them: float64 [n_tracks][cap][3], int32 [n_tracks]"""
+        n = np.ascontiguousarray(n_track_points, dtype=np.int32).reshape(-1)
+        return _d(tracks).reshape(n.size, self.cap, 3), n
+
     def cross_audit_tracks(self, pop, tracks, n_track_points, separation, step=False):
         """population pop's current paths against the caller's tracks [n_tracks][cap][3] of n_track_points [n_tracks]
         points each (pmaf_cross_audit_tracks): clearance [N][n_tracks], with step=True (clearance, step)"""
-        n = np.ascontiguousarray(n_track_points, dtype=np.int32).reshape(-1)
-        tr = _d(tracks).reshape(n.size, self.cap, 3)
+        tr, n = self._tracks(tracks, n_track_points)
         clr = np.zeros((self.N, n.size))
         st = np.zeros((self.N, n.size), dtype=np.int32) if step else None
         self._chk(self.L.pmaf_cross_audit_tracks(self._h, int(pop), n.size, _p(tr), _pi(n), float(separation), _p(clr), _pi(st)))
@@ -377,6 +381,10 @@ class PmafPlanner:
         cost, clr, feas = C.c_double(0), C.c_double(0), C.c_int32(0)
         self._chk(self.L.pmaf_select_pair(self._h, int(pop_a), int(pop_b), float(separation), float(margin), _pi(pair),
                                           C.byref(cost), C.byref(clr), C.byref(feas)))
+        return self._pair_dict(pair, cost, clr, feas)
+
+    @staticmethod
+    def _pair_dict(pair, cost, clr, feas):
         return {"pair": (int(pair[0]), int(pair[1])), "cost": cost.value, "clearance": clr.value, "feasible": bool(feas.value)}
 
     # -- cross audit with timing slack: A up to late_a steps behind B's clock, B up to late_b behind A's --
@@ -393,8 +401,7 @@ class PmafPlanner:
     def cross_audit_tracks_slack(self, pop, tracks, n_track_points, separation, late_a, late_b, steps=False):
         """population pop's current paths against the caller's tracks [n_tracks][cap][3] (pmaf_cross_audit_tracks_slack):
         clearance [N][n_tracks], with steps=True (clearance, step_a, step_b)"""
-        n = np.ascontiguousarray(n_track_points, dtype=np.int32).reshape(-1)
-        tr = _d(tracks).reshape(n.size, self.cap, 3)
+        tr, n = self._tracks(tracks, n_track_points)
         clr = np.zeros((self.N, n.size))
         sa = np.zeros((self.N, n.size), dtype=np.int32) if steps else None
         sb = np.zeros((self.N, n.size), dtype=np.int32) if steps else None
@@ -408,8 +415,7 @@ class PmafPlanner:
         cost, clr, feas = C.c_double(0), C.c_double(0), C.c_int32(0)
         self._chk(self.L.pmaf_select_pair_slack(self._h, int(pop_a), int(pop_b), float(separation), float(margin), int(late_a),
                                                 int(late_b), _pi(pair), C.byref(cost), C.byref(clr), C.byref(feas), _pi(st)))
-        return {"pair": (int(pair[0]), int(pair[1])), "cost": cost.value, "clearance": clr.value, "feasible": bool(feas.value),
-                "steps": (int(st[0]), int(st[1]))}
+        return dict(self._pair_dict(pair, cost, clr, feas), steps=(int(st[0]), int(st[1])))
 
     def link_force(self, link_pos, k_r_force, obstacles, pop=0):
         lp, k, o = _d(link_pos), _d(k_r_force), self._obs(obstacles)

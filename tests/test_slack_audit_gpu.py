@@ -240,6 +240,73 @@ def test_select_pair_slack_against_the_reference(pmaf, scenes, hip_lib):
         pl.close()
 
 
+def test_calls_of_every_kind_share_one_handles_scratch(pmaf, scenes, hip_lib):
+    """the six calls lay ONE grow-only scratch out per call (clearance | partials | result | tracks | step | track lengths
+    | second step matrix): on one handle, 3 tracks, then a slacked population audit (the second step matrix appears), then
+    T + 1 tracks slacked (the scratch grows and the second step matrix moves), a slacked pick, the plain audit, the plain
+    pick, and the first call again -- every output of every call against the two references at tolerance 0, the last
+    call's bits the first call's. Two chunks of steps, the second ragged."""
+    pl, arms, starts = coupled_handle(pmaf, scenes, 5, CH + 6)
+    try:
+        sc, order = arms[0], hip_lib.pmaf_eval_order()
+        pl.rollout()
+        pl.evaluate(sc["cost_gains"], sc["ws_limits"])
+        costs = np.asarray(pl.costs())
+        paths, n = _paths(pl)
+        cap = pl.cap
+        assert CH < cap < 2 * CH, "the horizon was meant to give a second, ragged chunk"
+        pop = [(paths[p].tolist(), n[p].tolist()) for p in (0, 1)]
+        rng = np.random.default_rng(11)
+
+        def make_tracks(n_tracks):
+            tracks = rng.uniform(-1.0, 1.0, (n_tracks, cap, 3))
+            tracks[:, :, 2] += 0.7
+            ntp = np.asarray(([cap, 0, cap // 2, 1] * n_tracks)[:n_tracks], dtype=np.int32)
+            for t in range(n_tracks):
+                tracks[t, ntp[t]:] = np.nan       # rows past the count are not read
+            return tracks, ntp
+
+        def same(got, want, what):
+            _same_bits(got[0], want[0], what + ": clearance")
+            for g, w, name in zip(got[1:], want[1:], ("step_a", "step_b")):
+                np.testing.assert_array_equal(g, np.asarray(w, dtype=np.int32), err_msg="%s: %s" % (what, name))
+
+        def same_pick(got, matrix, margin, what):
+            pair, cost, clr, feas = ref.select_pair(np.asarray(matrix).tolist(), costs[0].tolist(), costs[1].tolist(), margin)
+            assert got["pair"] == pair and got["feasible"] == bool(feas), (what, got, pair, feas)
+            _same_bits(np.asarray([got["cost"], got["clearance"]]), [cost, clr], what + ": pair cost / clearance")
+            return pair
+
+        few, n_few = make_tracks(3)
+        many, n_many = make_tracks(T + 1)
+        # 1. three tracks, step against step
+        first = pl.cross_audit_tracks(0, few, n_few, SEP, step=True)
+        want_first = ref.cross_audit(*pop[0], few.tolist(), n_few.tolist(), SEP, order)
+        same(first, want_first, "1. cross_audit_tracks")
+        # 2. the two populations, slacked, both step matrices
+        same(pl.cross_audit_slack(0, 1, SEP, 2, 1, steps=True), sref.cross_audit_slack(*pop[0], *pop[1], SEP, 2, 1, order),
+             "2. cross_audit_slack")
+        # 3. T + 1 tracks, slacked: a larger scratch, every part behind the matrix at another offset
+        same(pl.cross_audit_tracks_slack(1, many, n_many, SEP, 2, 1, steps=True),
+             sref.cross_audit_slack(*pop[1], many.tolist(), n_many.tolist(), SEP, 2, 1, order), "3. cross_audit_tracks_slack")
+        # 4. the slacked pick
+        want = sref.cross_audit_slack(*pop[0], *pop[1], SEP, 3, 2, order)
+        got = pl.select_pair_slack(0, 1, SEP, float(np.median(want[0])), 3, 2)
+        pair = same_pick(got, want[0], float(np.median(want[0])), "4. select_pair_slack")
+        assert got["steps"] == (int(np.asarray(want[1])[pair]), int(np.asarray(want[2])[pair]))
+        # 5. the plain audit, 6. the plain pick
+        want = ref.cross_audit(*pop[0], *pop[1], SEP, order)
+        same(pl.cross_audit(0, 1, SEP, step=True), want, "5. cross_audit")
+        same_pick(pl.select_pair(0, 1, SEP, float(np.median(want[0]))), want[0], float(np.median(want[0])), "6. select_pair")
+        # 7. the first call again
+        again = pl.cross_audit_tracks(0, few, n_few, SEP, step=True)
+        same(again, want_first, "7. cross_audit_tracks again")
+        _same_bits(again[0], first[0], "the first call's clearance")
+        np.testing.assert_array_equal(again[1], first[1])
+    finally:
+        pl.close()
+
+
 def _tick_run(pmaf, scenes, late, audit, n_ticks=4):
     pl, arms, starts = coupled_handle(pmaf, scenes, 5, 30)
     try:
