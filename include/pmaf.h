@@ -680,8 +680,14 @@ int pmaf_debug_withhold_mailbox(pmaf_planner *h, int32_t enable);
  * scalar through the guarded / the compiler's divide; 9 / 10: a / sqrt(b)
  * through the kernels' shared-reciprocal sequence / the compiler; 11 / 12: the
  * fixup-free a / b and a / sqrt(b) used where the divisor is a positive
- * normal). Tests compare the
- * results bitwise with the host's IEEE results. */
+ * normal; 13: the default policy's square root without its zero / infinity
+ * select, for a positive finite a). Tests compare the results bitwise with
+ * the host's IEEE results and with constructed hard-to-round operands
+ * (tests/hard_rounding.py).
+ * 14..17: the opt-in fast policy's operations, which carry an error bound
+ * instead: 14: a / b through its refined reciprocal, 15: its sqrt(a), 16: the
+ * reciprocal root y ~ 1 / sqrt(b) its norm sequence shares, 17: a / sqrt(b) as
+ * the product a * y that replaces the division by a norm. */
 int pmaf_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out);
 
 #ifdef __cplusplus

@@ -75,10 +75,16 @@ __device__ __forceinline__ double smin(double a, double b) { return (b < a) ? b 
 // How divisions and square roots are evaluated in the tuned rollout kernels.
 //
 // MATH_IEEE (0)  the compiler's expansions (v_div_scale .. v_div_fmas,
-//                v_div_fixup; v_rsq + Goldschmidt with range scaling):
-//                correctly rounded for every input. They serialise on VCC and
-//                cost 65-72 / 110 cycles each on a lone wave even when several
-//                are independent (tools/ubench.hip). PMAF_FLAG_IEEE_SEQUENCES.
+//                v_div_fixup; v_rsq + Goldschmidt with range scaling), meant
+//                to be correctly rounded for every input. The root's is on
+//                every constructed hard case; the division's returns the
+//                quotient 1 ulp low where its two Newton steps leave the
+//                neighbour of RN(1 / b): measured for divisor mantissas
+//                2^53 - 5, - 11, - 13 (3 of 2.5e6 constructed cases,
+//                tests/test_hard_rounding_gpu.py reports them). They serialise
+//                on VCC and cost 65-72 / 110 cycles each on a lone wave even
+//                when several are independent (tools/ubench.hip).
+//                PMAF_FLAG_IEEE_SEQUENCES.
 // MATH_XACT (2)  DEFAULT. The same Newton / Goldschmidt iterations written out
 //                without the range-scaling instructions, one refined reciprocal
 //                shared by the three components of a vector divided by its
@@ -86,14 +92,27 @@ __device__ __forceinline__ double smin(double a, double b) { return (b < a) ? b 
 //                operands whose exponents lie within +-250 (every quantity of
 //                this path for inputs in the validated range 2^-100..2^100:
 //                lengths in metres, speeds, gains) the hardware's scaling is
-//                the identity, so these sequences return the same bits as
-//                MATH_IEEE -- the whole GPU parity suite is bit-exact in both
-//                modes and test_xact_sequences_match_ieee sweeps the range.
-//                Outside it (denormal-scale operands) results stay accurate to
+//                the identity, so these sequences return the correctly
+//                rounded IEEE bits -- the whole GPU parity suite is bit-exact
+//                in both modes, test_xact_sequences_match_ieee sweeps the range
+//                with random operands, and tests/test_hard_rounding_gpu.py holds
+//                sqrt, sqrt_pos, div, div_pos and a / sqrt(b) through the shared
+//                reciprocal to 3.0e6 CONSTRUCTED operands whose exact result lies
+//                within 2^-37 ulp (quotients; most within 2^-43) or 2^-36 ulp
+//                (roots) of a rounding midpoint, or 2^-34 ulp beside a double,
+//                exponents over +-250, every divisor mantissa 2^53 - k and
+//                2^52 + k for odd k < 4096 among them: bit equality, sign of
+//                zero included. (That found rcp_refined, below, 1 ulp off for
+//                three divisor mantissas; with its third step the policy is
+//                correctly rounded there where the compiler's expansion is not.)
+//                Outside +-250 (denormal-scale operands) results stay accurate to
 //                rounding error but are not guaranteed bit-identical.
 // MATH_FAST (1)  opt-in (PMAF_FLAG_FAST_MATH): v_rcp_f64 / v_rsq_f64 seeds
 //                (2^-24) + two Newton iterations, no residual correction:
-//                1-2 ulp per operation; tolerance parity only.
+//                1-2 ulp per operation (measured on the constructed cases and
+//                1e6 random operands: a * rcp(b) 1.17 ulp, sqrt 1.14, the shared
+//                1 / sqrt(b) 1.56, x * rs 2.21 -- 0.53 of the 2^-51 per operation
+//                tests/hp_reference.py allows at most); tolerance parity only.
 // MATH_FMA (3)   opt-in (PMAF_FLAG_CONTRACTED, round 4): MATH_FAST's sequences AND
 //                the translation unit compiled with -ffp-contract=fast, so the
 //                step's dot / cross / axpy forms retire as v_fma_f64 (dot 5 -> 3,
@@ -163,13 +182,25 @@ template <> struct Mth<MATH_XACT> {
     g = __builtin_fma(d, h, g);
     return g;
   }
+  // RN(1 / b), the CORRECTLY ROUNDED reciprocal: div_r's single residual step returns the correctly rounded quotient
+  // only then (Markstein). Two Newton steps from the 2^-24 seed leave RN((1 / b)(1 - eps^2)), eps^2 ~ 2^-96: the
+  // neighbour of RN(1 / b) wherever 1 / b lies closer than that to the midpoint of two doubles -- b a few ulp below a
+  // power of two (1 / (1 - k 2^-53) is k^2 2^-106 above one), and sporadic others. With that reciprocal, 1 ulp low,
+  // 0x1.6666666666663p-1 / 0x1.ffffffffffffbp-1 came out 1 ulp low on the hardware (and k = 11, 13; the compiler's
+  // own expansion returns the same wrong bits; tests/test_hard_rounding_gpu.py). The third step starts within 1 ulp:
+  // its residual e = (B + j) 2^-106 is exact and RN(r + r e) = RN((1 / b)(1 - e^2)) is RN(1 / b) for every b but one
+  // mantissa, all ones, where r + r e is an exact tie between the two fixed points 2^-n and 2^-n (1 + 2^-52) of the
+  // step; RN(1 / b) is the odd one of the two, whichever the iteration sits on: the select sets its last bit.
   static __device__ __forceinline__ double rcp_refined(double b) {
     double r = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, r, 1.0);
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-b, r, 1.0);
     r = __builtin_fma(r, e, r);
-    return r;
+    e = __builtin_fma(-b, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    const bool ones = ((unsigned long long)__double_as_longlong(b) | 0xfff0000000000000ull) == ~0ull;
+    return __longlong_as_double(__double_as_longlong(r) | (long long)ones);
   }
   // a / b given r = rcp_refined(b); v_div_fixup supplies the IEEE results for
   // zero / infinite / NaN operands

@@ -2593,14 +2593,15 @@ int pmaf_reset_kernel_stats(pmaf_planner *h) {
 }
 int pmaf_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out) {
   return guarded([&] {
-    REQUIRE(a && b && out && n > 0 && op >= 0 && op <= 12, "pmaf_debug_math: bad argument");
+    REQUIRE(a && b && out && n > 0 && op >= 0 && op <= 17, "pmaf_debug_math: bad argument");
     double *da = nullptr, *db = nullptr, *dout = nullptr;
     HIP_CHECK(hipMalloc((void **)&da, sizeof(double) * n));
     HIP_CHECK(hipMalloc((void **)&db, sizeof(double) * n));
     HIP_CHECK(hipMalloc((void **)&dout, sizeof(double) * n));
     HIP_CHECK(hipMemcpy(da, a, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(db, b, sizeof(double) * n, hipMemcpyHostToDevice));
-    pmaf_k_launch_debug_math(op, n, da, db, dout, nullptr);
+    if (op <= 12) pmaf_k_launch_debug_math(op, n, da, db, dout, nullptr);
+    else pmaf_k_launch_debug_math_ext(op, n, da, db, dout, nullptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);

@@ -27,7 +27,8 @@ from mpmath.ctx_mp import MPContext
 PREC = 113
 U = 2.0 ** -53                 # unit roundoff of IEEE double: MATH_XACT, MATH_IEEE
 # MATH_FAST / MATH_FMA: csrc/pmaf_device.hpp documents the v_rcp_f64 / v_rsq_f64 seeds plus two Newton (Goldschmidt)
-# iterations as "1-2 ulp per operation". 2 ulp of a result r is at most 2 * 2^-52 |r|.
+# iterations as "1-2 ulp per operation". 2 ulp of a result r is at most 2 * 2^-52 |r|. Measured since
+# (tests/test_hard_rounding_gpu.py, constructed hard cases + 1e6 random operands): at most 0.53 of this per operation.
 EPS_FAST = 2.0 ** -51
 # the restated exp (glibc's algorithm, 0.511 ulp; test_device_arithmetic_is_ieee_exact holds the kernels' exp to it bit
 # for bit): 1 ulp <= 2^-52 relative
