@@ -19,10 +19,6 @@
 #include "pmaf_types.hpp"
 #include "pmaf_lpa_model.hpp"
 
-#ifndef PMAF_W64_SLICE_DEFAULT
-#define PMAF_W64_SLICE_DEFAULT true
-#endif
-
 using namespace pmaf;
 
 static thread_local std::string g_err;
@@ -874,10 +870,9 @@ int pmaf_create(const pmaf_params *prm, pmaf_planner **out) {
     //   BASELINE C5, two scenes in the handle (its per-GPU load at 4 GPUs): 386 -> 372.  Settings 2^8 ... 2^10 x 4 ... 6 of 8: within 2 %.
     // The arithmetic and its order are the same instructions: bit-identical results (tests/test_parity_gpu.py runs these shapes).
     // PMAF_W64_SLICE=0|1, PMAF_W64_SLICE_LOG2, PMAF_W64_SLICE_YOUNGER in the environment: timing experiments.
-    { const char *e = getenv("PMAF_W64_SLICE"); h->w64_slice = e ? (e[0] == '1') : PMAF_W64_SLICE_DEFAULT; }
+    { const char *e = getenv("PMAF_W64_SLICE"); h->w64_slice = e ? (e[0] == '1') : true; }
     { const char *e = getenv("PMAF_W64_SLICE_LOG2"); D.prio_slice_log2 = std::min(20, std::max(4, e ? atoi(e) : 9)); }       // (a shift count on the device)
     { const char *e = getenv("PMAF_W64_SLICE_YOUNGER"); D.prio_younger_of_8 = std::min(7, std::max(1, e ? atoi(e) : 5)); }
-    { const char *ab = getenv("PMAF_ABLATE"); D.ablate = ab ? atoi(ab) : 0; }
     { const char *to = getenv("PMAF_EXCHANGE_TIMEOUT_S"); if (to && atof(to) > 0.0) h->exchange_timeout_s = atof(to); }
     { const char *to = getenv("PMAF_TICK_TIMEOUT_S"); if (to && atof(to) > 0.0) h->tick_timeout_s = atof(to); }
     // ordered force sum: the DPP chain for every obstacle count (round 3: with the first chunk's accumulates fused and

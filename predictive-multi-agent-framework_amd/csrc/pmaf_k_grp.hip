@@ -25,18 +25,9 @@ using namespace pmaf;
 //   population: the wave index is rotated by 8 per population so that two such waves do not share a SIMD (-3 %).
 //   Re-swept in round 3 on the shorter step (profiles/r3_ab_session3.txt item 11): 6 slices of 8 for the younger wave, slices of
 //   2^9 ticks (5 us): 736 us against 761 us with the round-2 setting (5 of 8, 2^10), 746 (6, 2^10), 752 (6, 2^8), 776 (7, 2^10).
-#ifndef PMAF_PRIO_SLICE_LOG2
-#define PMAF_PRIO_SLICE_LOG2 9
-#endif
-#ifndef PMAF_PRIO_YOUNGER_OF_8
-#define PMAF_PRIO_YOUNGER_OF_8 6
-#endif
-constexpr int PRIO_SLICE_LOG2 = PMAF_PRIO_SLICE_LOG2;       // 2^9 ticks of the 100 MHz wall clock
-constexpr unsigned PRIO_YOUNGER_OF_8 = PMAF_PRIO_YOUNGER_OF_8;
-#ifndef PMAF_POP_ROTATE
-#define PMAF_POP_ROTATE 8
-#endif
-constexpr unsigned POP_ROTATE = PMAF_POP_ROTATE;
+constexpr int PRIO_SLICE_LOG2 = 9;       // 2^9 ticks of the 100 MHz wall clock
+constexpr unsigned PRIO_YOUNGER_OF_8 = 6;
+constexpr unsigned POP_ROTATE = 8;
 template <int LPA, int TILES, int MATH, bool STATIC>
 __device__ __forceinline__ void rollout_grp_body(const DevView &D, const CostParams &CP) {
   extern __shared__ double smem[];
@@ -54,13 +45,10 @@ __device__ __forceinline__ void rollout_grp_body(const DevView &D, const CostPar
   const int n_obs = D.n_obs;
   const int M = n_obs - 1;
   PopConst C = D.C;
-#ifndef PMAF_GRP_PIN
-#define PMAF_GRP_PIN 1
-#endif
   // STATIC body (round 4): the obstacles' velocities no longer hold registers, so the population constants are pinned in
   // VGPRs (as in the wave-per-agent kernel): left in the SGPR file they are spilled to VGPR lanes and reloaded by
   // v_readlane in the step loop -- VALU instructions, which bound this kernel (profiles/r6_c5_strict_steploop.txt)
-  if (STATIC && PMAF_GRP_PIN) {
+  if (STATIC) {
     double *f = reinterpret_cast<double *>(&C);
     for (int i = 0; i < (int)(sizeof(PopConst) / sizeof(double)); i++) asm volatile("" : "+v"(f[i]));
   }
@@ -135,10 +123,7 @@ __device__ __forceinline__ void rollout_grp_body(const DevView &D, const CostPar
   // sequences (~110 VALU instructions per step of a VALU-issue-bound kernel). Lanes 0 / 1 / 2 of each row now carry the
   // three vectors through ONE sequence (the w64 kernel's idle-lane riders) and the results come back by DPP
   // row_newbcast moves: the same operations on the same operands, so the same bits.
-#ifndef PMAF_GRP_PACK
-#define PMAF_GRP_PACK 1
-#endif
-  constexpr bool PACK = PMAF_GRP_PACK && (LPA >= 16);
+  constexpr bool PACK = LPA >= 16;
   const double inv_shell = 1.0 / C.shell;   // (sentinel_repel_m)
   const int rsub = sub & 15;
   const bool l_nv = (rsub == 1), l_des = (rsub == 2);
@@ -277,13 +262,8 @@ __global__ __launch_bounds__(64) void k_rollout_grp(DevView D, CostParams CP) {
                              bz = (unsigned long long)__double_as_longlong(src[5 * n_obs + i]);
     rest = rest && ((bx | by | bz) == 0ull);
   }
-#ifdef PMAF_GRP_FORCE_STATIC   // register-budget experiments only: the STATIC body alone
-  (void)rest;
-  rollout_grp_body<LPA, TILES, MATH, true>(D, CP);
-#else
   if (!wave_any(!rest)) rollout_grp_body<LPA, TILES, MATH, true>(D, CP);
   else rollout_grp_body<LPA, TILES, MATH, false>(D, CP);
-#endif
 }
 
 #ifndef PMAF_GRP_MATH

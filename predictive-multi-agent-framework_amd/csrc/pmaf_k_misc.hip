@@ -207,7 +207,7 @@ __device__ __forceinline__ void real_step_w64(const DevView &D, const double dt_
   SecTimers ST;
   if (gate)
     circ_and_scale_w64<TILES, T_REAL, MATH_XACT>(lane, rp, rv, zv, goal, g, dg, gn, C, k_circ, n_obs, rot_g, known_bits,
-                                                 O, clist, no_min, F, scale, ST, exp_consts(), 0, htype);
+                                                 O, clist, no_min, F, scale, ST, exp_consts(), htype);
   F = F + (mk(0.0, 0.0, 0.0) + repel);
   if (k_attr != 0.0) F = F + (scale * k_damp) * verr;
   F_total = F;
@@ -237,17 +237,6 @@ __device__ __forceinline__ void real_step_w64(const DevView &D, const double dt_
 // obstacles inside the real agent's shell.
 __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, ManagerArgs A) {
   extern __shared__ double smem[];
-#ifdef PMAF_TICK_STAMPS
-  const unsigned long long t_mgr0 = wall_clock64();
-#endif
-#ifdef PMAF_MGR_SECTIONS   // timing experiments only: where the manager step's time goes (10 ns ticks, printed by population 0)
-  unsigned long long t_sec[8];
-  int n_sec = 0;
-#define PMAF_MSEC() do { __builtin_amdgcn_s_waitcnt(0); t_sec[n_sec++] = wall_clock64(); } while (0)
-#else
-#define PMAF_MSEC() do { } while (0)
-#endif
-  PMAF_MSEC();
   const int lane = threadIdx.x;
   const int pop = blockIdx.x;
   const int n_obs = D.n_obs;
@@ -260,15 +249,12 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
   double *s_cost = smem + 7 * n_obs + (n_obs + 1) / 2;
 
   // ---- loads that depend on nothing ----
-#ifndef PMAF_MGR_EARLY_RESULTS
-#define PMAF_MGR_EARLY_RESULTS 1
-#endif
   // the rollout's per-agent results (first four agents of every lane = all of them up to 256 agents): requested before
   // anything else, so that their round trip runs under the obstacle table's instead of behind it (round 5, device-side
   // duration of this kernel in back-to-back C2 ticks: 11.05 -> 10.5 us; the same for every agent's gains and type, to take
   // the selected agent's out of a lane's registers after the argmin, was measured SLOWER: 11.3 us)
   double cw_pre[4], gd_pre[4], pl_pre[4], mo_pre[4];
-  if (PMAF_MGR_EARLY_RESULTS && A.do_select) {
+  if (A.do_select) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int a = lane + 64 * k;
@@ -373,7 +359,6 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
   int health = 0;   // PMAF_HB_* bits of this tick (mailbox entry 15; wave-uniform)
   // random vectors the real agent's heuristic uses (best_agent_'s copy)
   const double *rand_g = D.best_rnd + (size_t)pop * 3 * n_obs;
-  PMAF_MSEC();   // 1: up-front loads, live obstacles in LDS
 
   if (A.do_select) {
     // cost assembly + argmin, B/src/cf_manager.cpp:325-343
@@ -384,7 +369,7 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
     // the 15 us manager kernel at 1024 agents; same operations per agent, ascending agent index per lane as before)
     for (int a0 = lane; a0 < N; a0 += 256) {
       double cw[4], gdv[4], pl[4], mov[4];
-      if (PMAF_MGR_EARLY_RESULTS && a0 == lane) {
+      if (a0 == lane) {
 #pragma unroll
         for (int k = 0; k < 4; k++) { cw[k] = cw_pre[k]; gdv[k] = gd_pre[k]; pl[k] = pl_pre[k]; mov[k] = mo_pre[k]; }
       } else {
@@ -445,7 +430,6 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
     best = min_idx;
     if (lane == 0) D.best_idx[pop] = best;
   }
-  PMAF_MSEC();   // 2: selection
   if (A.do_move) {
     // RealCfAgent::cfPlanner one step, B/src/cf_agent.cpp:343-366
     int gid = A.agent_id_inline ? A.agent_id_val[pop] : (A.agent_id ? A.agent_id[pop] : best);
@@ -504,7 +488,6 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
     }
   }
 
-  PMAF_MSEC();   // 3: the real agent's step
   // header of this population's winner record (sharded runs): the selection just made, with the path length the
   // selected agent's rollout had when it was scored and the set-point the real agent moves to. Written BEFORE the
   // mailbox's sequence number (system-scope fence below): once the host has seen that number the header is visible
@@ -582,7 +565,6 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
     }
   }
 
-  PMAF_MSEC();   // 4: published (mailbox, fence)
   // winner path (pmaf_enable_winner_path): the selected agent's path AS IT WAS SCORED, into mapped pinned host memory,
   // behind the set-point (which the caller waits for first) and before the rollout launched next overwrites the buffer
   // (stream order). 24 B per point over PCIe; its own sequence word last, behind a system-scope fence.
@@ -654,16 +636,6 @@ __global__ __launch_bounds__(64) void k_manager(DevView D, CostParams CP, Manage
       if (lane == 0) D.closest_ok[pop] = mv ? 0 : 1;
     }
   }
-#ifdef PMAF_TICK_STAMPS
-  if (lane == 0 && pop == 0) printf("M %llu %llu\n", t_mgr0, wall_clock64());
-#endif
-#ifdef PMAF_MGR_SECTIONS
-  PMAF_MSEC();   // 5: reset
-  if (lane == 0 && pop == 0)
-    printf("MGR loads %llu select %llu real-step %llu publish %llu reset %llu | total %llu (x10 ns)\n", t_sec[1] - t_sec[0],
-           t_sec[2] - t_sec[1], t_sec[3] - t_sec[2], t_sec[4] - t_sec[3], t_sec[5] - t_sec[4], t_sec[5] - t_sec[0]);
-#endif
-#undef PMAF_MSEC
 }
 
 // CfAgent::setPosition for every predicted agent (clear + push_back,

@@ -73,13 +73,10 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
 
   LaneObstacles<TILES> O;
   unsigned known_bits = 0u;
-#ifndef PMAF_CLOSEST_TABLE
-#define PMAF_CLOSEST_TABLE 1
-#endif
   // closest-other table (below): the multi-slot kernels' Obstacle / GoalObstacle bodies only -- with one slot per lane
   // the search is one sqrt chain + two reductions, the GoalObstacle agent does not bound the C2 launch without it, and
   // the short C1 rollout would pay for the table's loads in its prologue (measured: profiles/r3_ab_session3.txt)
-  constexpr bool USES_CLOSEST = PMAF_CLOSEST_TABLE && TILES >= 2 && (TYPE == T_OBST || TYPE == T_GOALOBST);
+  constexpr bool USES_CLOSEST = TILES >= 2 && (TYPE == T_OBST || TYPE == T_GOALOBST);
 #pragma unroll
   for (int t = 0; t < TILES; t++) {
     int i = t * 64 + lane;
@@ -146,19 +143,16 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
     // it would turn into +0.0, and the goal direction read back from lane 63 also feeds the latch, calc_rot_vec_pre)
     const double nz = (C.dt < 0.0) ? 0.0 : -0.0;
     if (lane == 63 || lane == 61) { O.p[0] = goal; O.v[0] = mk(nz, nz, nz); }
-#ifndef PMAF_SENT_RIDER
-#define PMAF_SENT_RIDER 1
-#endif
     // Round 4 (last session): the loop that carries code for the repulsive obstacle keeps that obstacle in lane 60 like a
     // field obstacle (advanced with the others by predictObstacles' p + v dt), so that |p - sent_pos| and the direction
     // to it -- repelForce's square root, reciprocal and three divisions -- ride in the tail's ONE sequence like the goal
     // and the two speed limits (the one-slot kernel therefore takes at most 60 field obstacles; the host sends 61..64
     // to the other kernels). C4, where the obstacle is the other arm: 280.0 -> 270.5 us per launch
     // (profiles/r4_ab_w64.txt item 8).
-    if (PMAF_SENT_RIDER && SENT == 1 && lane == 60) { O.p[0] = sent_p; O.v[0] = sent_v; }
+    if (SENT == 1 && lane == 60) { O.p[0] = sent_p; O.v[0] = sent_v; }
     MT::norm_unit(O.p[0] - p, s_pre, ron_pre);
   }
-  constexpr bool SRIDE = PMAF_SENT_RIDER && PRE && SENT == 1;
+  constexpr bool SRIDE = PRE && SENT == 1;
   V3 verr = attractor_velocity_error<MATH>(v, g, C, k_attr, k_damp);
   const double zsent_lt = D.zsent_lt[pop];
   const bool sent_reachable = (SENT == 2) ? sentinel_reachable(p, sent_p, sent_v, zsent_lt, C, D.cap) : (SENT == 1);
@@ -205,13 +199,9 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
     double scale = 1.0;
     PMAF_SEC(ST, 0);
     // (called with the gate closed too: the sweep's few compares then find no obstacle -- one branch less in the step)
-#ifdef PMAF_ABLATION   // timing experiments only (PMAF_ABLATE=8: no sweep in the multi-slot kernels)
-    if (PRE || (gate && !(D.ablate & 8)))
-#else
     if (PRE || gate)
-#endif
       circ_and_scale_w64<TILES, TYPE, MATH, PRE, DPPSUM, decltype(EK), (STATICV ? (SENT == 1 ? 59 : 60) : -1)>(lane, p, v, zv, goal, g, dg, gn, C, k_circ, n_obs, rot_g, known_bits,
-                                                 O, clist, lane_min, F, scale, ST, EK, D.ablate, 0, s_pre, ron_pre,
+                                                 O, clist, lane_min, F, scale, ST, EK, 0, s_pre, ron_pre,
                                                  gate_m, cidx);
     PMAF_SEC(ST, 5);
     // attractorForce (:183-193), updatePositionAndVelocity (:253-268)
@@ -345,14 +335,7 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
 #ifdef PMAF_SECTION_TIMERS
   const unsigned long long t_loop_end = wall_clock64();
 #endif
-#ifdef PMAF_ABL_NOCOST     // timing experiments only: no path-cost pass after the loop
-  cost_ws = 0.0; path_len = 0.0;
-#else
   path_cost_terms_w64<MATH>(lane, path, n, CP.ws, CP.k_workspace, clist, cost_ws, path_len);
-#endif
-#ifdef PMAF_TICK_STAMPS   // absolute device wall clock (100 MHz) of every wave's start / end: where a tick's time goes
-  if (lane == 0 && pop == 0) printf("R %d %llu %llu\n", a, t_begin, wall_clock64());
-#endif
 #ifdef PMAF_SECTION_TIMERS
   if (lane == 0 && pop == 0 && a < 7)
     printf("agent %d: loop %llu0 ns, path-cost pass %llu0 ns (%d points)\n", a, t_loop_end - t_begin, wall_clock64() - t_loop_end, n);
@@ -466,10 +449,6 @@ bool PMAF_W64_LAUNCH(const DevView &D, const CostParams &cp, int tiles, bool dpp
   const dim3 g64((unsigned)D.N, (unsigned)D.P), block(64);
 #define PMAF_L(K) hipExtLaunchKernelGGL(K, g64, block, (unsigned)lds, s, e0, e1, 0, D, cp)
   // one slot per lane: both ordered-sum variants (the host picks); two / four slots: DPP only
-#ifdef PMAF_ONLY_W64_1_DPP   // tools/slackprof: a translation unit that holds the C2 kernel alone (same ISA as the product's)
-  if (tiles <= 1 && dppsum && plain) { PMAF_L((k_rollout_w64<1, PMAF_W64_MATH, true, true>)); return true; }
-  return false;
-#endif
 #define PMAF_LP(T, S) do { if (plain) PMAF_L((k_rollout_w64<T, PMAF_W64_MATH, S, true>)); \
                            else PMAF_L((k_rollout_w64<T, PMAF_W64_MATH, S, false>)); } while (0)
 #if !defined(PMAF_W64_PART) || PMAF_W64_PART == 1

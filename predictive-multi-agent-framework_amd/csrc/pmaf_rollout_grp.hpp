@@ -212,11 +212,7 @@ __device__ __forceinline__ void circ_and_scale_grp(lmask act_m, int sub, int grp
         MT::norm_rcp_zpos(zrv, vn, rvn);
         nv = MT::div3_n_pos(rv, vn, rvn);
       }
-#ifndef PMAF_GRP_CURVEC
-#define PMAF_GRP_CURVEC 1
-#endif
-      const V3 cur = PMAF_GRP_CURVEC ? current_vector_grp<MATH>(type, rv, nv, zrv, g, ron, rot)
-                                     : current_vector<MATH, true>(type, rv, g, ron, rot);
+      const V3 cur = current_vector_grp<MATH>(type, rv, nv, zrv, g, ron, rot);
       const V3 c = MT::div_pos(k_circ, d * d) * unit_triple<MATH>(nv, cur);   // nv x (cur x nv); d >= 1e-5
       const lmask m = in_m & PMAF_BAL(zrv != 0);   // vel_norm != 0, B/src/cf_agent.cpp:98
       if (PMAF_LANE(m)) {
@@ -232,10 +228,7 @@ __device__ __forceinline__ void circ_and_scale_grp(lmask act_m, int sub, int grp
     wave_lds_fence();
     // F = ((0 + c_0) + c_1) + ... per group; a group that has run out of terms adds +0.0 (exact no-op)
     // (lanes past their group's last term read the group's all-zero slot)
-#ifndef PMAF_GRP_SUM3
-#define PMAF_GRP_SUM3 1
-#endif
-    if (PMAF_GRP_SUM3 && LPA >= 16) {
+    if (LPA >= 16) {
       // Round 3: the three component sums in three LANES of each DPP row (row lane 0 adds the x of every entry, 1 the y,
       // 2 the z: ONE v_add_f64 per entry instead of three in this VALU-issue-bound kernel; the per-lane ds_read is not a
       // VALU instruction), read back by row_newbcast moves. Same additions in the same order per component. (F enters

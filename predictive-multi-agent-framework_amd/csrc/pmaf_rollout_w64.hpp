@@ -212,13 +212,13 @@ struct SecTimers {};
 // restart, and the compiler lays a conditional block out inline (branch taken to skip it) unless it knows the block is
 // cold. The step's rare blocks (first-contact latch, acceleration clamp, lists of more than 16 terms, nothing inside
 // the shell) are therefore wave-uniform conditions marked unlikely: the common path falls through.
-#ifndef PMAF_EXPECT
-#define PMAF_EXPECT 1
-#endif
-#if PMAF_EXPECT
 #define PMAF_RARE(c) __builtin_expect(!!(c), 0)
-#else
-#define PMAF_RARE(c) (c)
+
+// PMAF_SUM_TAIL_PIN (0 / 1, set per translation unit by build.sh): the one-slot DPP sum keeps the tail of the attractor-
+// scaling chain in the block of the ordered sum's first chunk, see circ_and_scale_w64. Only the default policy's
+// one-slot unit sets it.
+#ifndef PMAF_SUM_TAIL_PIN
+#define PMAF_SUM_TAIL_PIN 0
 #endif
 
 // Lane predicates as wave-uniform 64-bit MASKS (round 3). The compiler keeps a per-lane bool in an SGPR pair anyway, but a
@@ -357,7 +357,7 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
                                                    int n_obs, double *rot_g, unsigned &known_bits,
                                                    LaneObstacles<TILES> &O, double *clist, double &lane_min,
                                                    V3 &F, double &scale, SecTimers &ST, const KT &EK,
-                                                   const int ablate = 0, const int rtype = 0,
+                                                   const int rtype = 0,
                                                    const double s_pre = 0.0, const V3 ron_pre = V3{0.0, 0.0, 0.0},
                                                    const lmask gate_m = ~0ull, const int32_t *cidx = nullptr) {
   typedef Mth<MATH> MT;
@@ -411,14 +411,8 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
     any_in_m |= in_m[t];
   }
   PMAF_SEC(ST, 1);
-#ifdef PMAF_ABLATION   // timing experiments only (PMAF_ABLATE=4): no in-shell block
-  if (ablate & 4) return;
-#endif
   if (PMAF_RARE(any_in_m == 0ull)) return;  // nothing inside the shell: F stays 0, scale stays 1
   PMAF_CNT(ST, 0, 1);
-#ifndef PMAF_LDS_MIN
-#define PMAF_LDS_MIN 1
-#endif
   // Round 3: the wave minimum of the lanes' closest distances (attractorForceScaling's min_dist) through ONE LDS cell:
   // every lane stores the start value, then applies an atomic unsigned-64 minimum with its own distance (non-negative
   // doubles order like their bit patterns; a minimum is exact and order-independent), and the scaling chain reads the
@@ -429,7 +423,7 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   unsigned long long *min_cell = reinterpret_cast<unsigned long long *>(clist + MIN_CELL);
   // (kernels with long lists only: with the few obstacles of the LDS-batch variant -- C1: nine -- there is not enough
   // work between the atomic and the read to cover the round trip: C1 136.7 -> 140.6 us, measured)
-  constexpr bool LDSMIN = PMAF_LDS_MIN && DPPSUM;
+  constexpr bool LDSMIN = DPPSUM;
   if (LDSMIN) {
     wave_lds_fence();
     *reinterpret_cast<double *>(min_cell) = C.shell;   // every lane, same address, same value
@@ -462,13 +456,10 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   // ======== straight-line region ========
   // ---- circular-field terms (:97-106), evaluated by every lane (lanes outside
   // the shell compute values that go to their scratch entry)
-#ifndef PMAF_MIN_MID
-#define PMAF_MIN_MID 1
-#endif
   int count = 0;
   double m_mid = 0.0;
   // (two slots only: the four-slot kernel skips slots that hold nothing inside the shell, the last one included)
-  constexpr bool MIN_MID = PMAF_MIN_MID && TILES == 2;
+  constexpr bool MIN_MID = TILES == 2;
 #pragma unroll
   for (int t = 0; t < TILES; t++) {
     if (TILES > 2 && in_m[t] == 0ull) continue;  // no term from this slot (wave-uniform; 2 slots: both in one block)
@@ -518,11 +509,7 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
       m_mid = __longlong_as_double((long long)__hip_atomic_load(min_cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifdef PMAF_ABL_NOCIRC   // timing experiments only (tools/ablate.sh): no circular-term arithmetic, list traffic kept
-    const V3 c = rv; (void)nv; (void)cur; (void)rot;
-#else
     const V3 c = MT::div_pos(k_circ, d_t[t] * d_t[t]) * unit_triple<MATH>(nv, cur);  // nv x (cur x nv); d >= 1e-5
-#endif
     // compact the contributing terms, ascending obstacle index
     const unsigned long long m = in_m[t] & PMAF_BAL(zrv != 0);   // vel_norm != 0, B/src/cf_agent.cpp:98
     const bool has_c = PMAF_LANE(m);
@@ -556,29 +543,18 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
     e[0] = 0.0; e[1] = 0.0; e[2] = 0.0;
   }
   PMAF_CNT(ST, 1, count);
-#ifndef PMAF_SUM_HOIST
-#define PMAF_SUM_HOIST 3
-#endif
-#ifndef PMAF_SUM_FMAC1
-#define PMAF_SUM_FMAC1 1
-#endif
   // The first chunk of the list is fetched HERE, in front of the attractor-scaling chain (round 3): issued behind the
   // compaction stores (a wave's DS instructions execute in order), its LDS round trip runs under that chain instead
   // of in front of the sum, where the disassembly showed ds_read / s_waitcnt lgkmcnt(0) back to back. (An empty list
   // reads the all-zero padding chunk: the sum below needs no `count > 0` test for it.)
-  constexpr bool HOIST1 = DPPSUM && TILES == 1 && (PMAF_SUM_HOIST & 1);
-  constexpr bool HOISTN = DPPSUM && TILES >= 2 && (PMAF_SUM_HOIST & 2);
   double e_first = 0.0;
-  if (HOIST1 || HOISTN) {
+  if (DPPSUM) {
     wave_lds_fence();
     e_first = clist[lane];
   }
 
   // ---- attractorForceScaling value (:212-226), branchless ----
   double sc;
-#ifdef PMAF_ABL_NOSCALE    // timing experiments only: no attractor-scaling chain
-  sc = 1.0;
-#else
   {
     double m;
     // (round 4: reading the minimum back earlier -- in front of the circular terms -- costs the one-slot kernels 2-3 %
@@ -606,35 +582,30 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
         bi = ct ? (t * 64 + __ffsll((long long)ct) - 1) : bi;
       }
     }
-    // (the chunk fetched above is not touched before the closest-obstacle reduction is through: the scheduler, left
-    // alone, starts the sum ten instructions behind the ds_read and waits for it there)
-    if (HOIST1 && (PMAF_SUM_HOIST & 4)) asm("" : "+v"(e_first) : "s"(bi));
+    // (the scheduler, left alone, starts the sum ten instructions behind the chunk's ds_read above and waits for it
+    // there; tying the chunk to the closest-obstacle reduction's result to hold it back never shipped)
     const bool stall = (dot(g, v) <= 0.0) && (zv < C.zv09_lt) && (dg > 0.15);  // norm(v) < vmax - 0.1 vmax
     // (shell == 0: nothing is ever inside it, bi stays "none" and w is discarded)
     // (m in [1e-5, shell) whenever an obstacle is in reach; otherwise bi is "none" and w is discarded)
-#ifndef PMAF_EXP_STAGED
-#define PMAF_EXP_STAGED 1
-#endif
     double w1;
-    if (PMAF_EXP_STAGED && TILES >= 2) {   // (constants out of LDS: requested a stage ahead, pmaf_device.hpp)
+    if (TILES >= 2) {   // (constants out of LDS: requested a stage ahead, pmaf_device.hpp)
       typename std::remove_const<KT>::type EKs = EK;
       double m_in = m;
       const ExpHead H = exp_head(EKs, m_in);
       w1 = 1 - portable_exp_nonpos_staged(-MT::div_pos(MT::sqrt_pos(m_in), C.shell), EKs, H);
     }
     ExpPend EP;
-    if (!(PMAF_EXP_STAGED && TILES >= 2)) EP = portable_exp_nonpos_begin(-MT::div_pos(MT::sqrt_pos(m), C.shell), EK);
+    if (TILES == 1) EP = portable_exp_nonpos_begin(-MT::div_pos(MT::sqrt_pos(m), C.shell), EK);
     // |ro| and g.ro of the closest obstacle were computed by the lane that
     // owns it (same operands, same bits as recomputing them here)
     const int bl = bi & 63;
     const double sb = readlane_d(best_s, bl), gr = readlane_d(best_gr, bl);
     double w2 = 1 - MT::div(gr, dg * sb);
     w2 = w2 * w2;
-    if (!(PMAF_EXP_STAGED && TILES >= 2)) w1 = 1 - portable_exp_nonpos_end(EP);   // (the table entry has had w2's division to arrive)
+    if (TILES == 1) w1 = 1 - portable_exp_nonpos_end(EP);   // (the table entry has had w2's division to arrive)
     const double w = w1 * w2;
     sc = (bi == 0x7fffffff) ? 1.0 : (stall ? 0.0 : w);
   }
-#endif
 
   // ---- F = ((0 + c_0) + c_1) + ... front to back; every lane reads the same
   // address (LDS broadcast), so every lane ends with the same F. The list is
@@ -644,14 +615,12 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   // accesses for the COMPILER -- without them it may reorder or forward its own
   // LDS accesses (observed: wrong sums); the hardware executes a wave's DS
   // instructions in order, so no instruction is emitted for them.
-#ifndef PMAF_ABL_NOSUM     // (timing experiments only: without the ordered sum F stays 0)
   if (DPPSUM) {
   // F = ((0 + c_0) + c_1) + ... in ascending obstacle index, WITHOUT an LDS round trip per batch: one ds_read per 16
   // entries puts x_k / y_k / z_k of entry k into lane k of rows 0 / 1 / 2, and one DPP row_newbcast:k move per entry
   // feeds a single v_add_f64 that advances all three component sums at once (row 0 sums x, row 1 y, row 2 z). The
   // moves do not depend on the accumulator, so the dependent chain is ONE add per entry; entries past the end of the
   // list are +0.0 (exact no-op; skipping them in groups of 4 or 8 costs more in branches than the adds: measured).
-  if (!(HOIST1 || HOISTN)) wave_lds_fence();
   {
     double acc = 0.0;
     if (TILES >= 2) {
@@ -666,12 +635,9 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
     // Round 3: the next chunk's ds_read is in flight while this chunk is added (one register pair more).
     double one = 1.0;
     asm volatile("" : "+v"(one));
-    double e = HOISTN ? e_first : 0.0;
+    double e = e_first;
     int c16 = 0;
-#ifndef PMAF_SUM_PEELN
-#define PMAF_SUM_PEELN 1
-#endif
-    if (HOISTN && PMAF_SUM_PEELN) {
+    {
       // Round 3: the FIRST chunk as sixteen separate statements in the block of the attractor-scaling chain. A fused
       // accumulate needs two issue slots of distance to the next one, so a chunk in one asm block is 16 instructions in
       // 32 slots; the scaling chain (sqrt -> divide -> exp -> divide) is a second dependent chain with the same
@@ -690,9 +656,7 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
       asm volatile("" : : "v"(sc));          // the scaling value is complete in THIS block (not sunk behind the loop)
     }
     for (; c16 < count; c16 += 16) {
-      double en = 0.0;
-      if (HOISTN) en = clist[((c16 + 16) << 2) + lane];   // (behind the last chunk: padding / scratch, never used)
-      else e = clist[(c16 << 2) + lane];
+      const double en = clist[((c16 + 16) << 2) + lane];   // (behind the last chunk: padding / scratch, never used)
 #define PMAF_FM(K) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
       asm volatile("s_nop 4\n\t"
                    PMAF_FM(0) PMAF_FM(1) PMAF_FM(2) PMAF_FM(3) PMAF_FM(4) PMAF_FM(5) PMAF_FM(6) PMAF_FM(7)
@@ -700,16 +664,14 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
                    "s_nop 1"
                    : "+v"(acc) : "v"(e), "v"(one));
 #undef PMAF_FM
-      if (HOISTN) e = en;
+      e = en;
     }
     } else {
 #define PMAF_BC(K) acc = acc + __builtin_amdgcn_update_dpp(e, e, 0x150 + K, 0xf, 0xf, true);
 #define PMAF_BC16 PMAF_BC(0) PMAF_BC(1) PMAF_BC(2) PMAF_BC(3) PMAF_BC(4) PMAF_BC(5) PMAF_BC(6) PMAF_BC(7) \
                   PMAF_BC(8) PMAF_BC(9) PMAF_BC(10) PMAF_BC(11) PMAF_BC(12) PMAF_BC(13) PMAF_BC(14) PMAF_BC(15)
-    if (HOIST1) {
       // the first chunk unconditionally, in the block of the scaling chain (its 16 dependent adds interleave with that
       // chain's instructions; no branch, no loop for the common list of <= 16 terms); longer lists continue in a loop
-#if PMAF_SUM_FMAC1
       {
         // round 3: move + add fused here too (v_fmac_f64_dpp acc += row_newbcast:k(e) * 1.0, exact) -- as SIXTEEN separate
         // statements, so that the scheduler still interleaves them with the scaling chain (the single block of the
@@ -726,22 +688,13 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
         PMAF_FM1(8) PMAF_FM1(9) PMAF_FM1(10) PMAF_FM1(11) PMAF_FM1(12) PMAF_FM1(13) PMAF_FM1(14) PMAF_FM1(15)
 #undef PMAF_FM1
       }
-#else
-      { const double e = e_first; PMAF_BC16 }
-#endif
       // (keeps the rest of the scaling chain in THIS block, in front of the rare loop: left alone the compiler sinks
       // it behind the loop, where it can no longer interleave with the 16 dependent adds)
-      if (PMAF_SUM_HOIST & 8) asm volatile("" : : "v"(sc), "v"(acc));
+      if (PMAF_SUM_TAIL_PIN) asm volatile("" : : "v"(sc), "v"(acc));
       for (int c16 = 16; PMAF_RARE(c16 < count); c16 += 16) {
         const double e = clist[(c16 << 2) + lane];
         PMAF_BC16
       }
-    } else {
-    for (int c16 = 0; c16 < count; c16 += 16) {
-      const double e = clist[(c16 << 2) + lane];
-      PMAF_BC16
-    }
-    }
 #undef PMAF_BC16
 #undef PMAF_BC
     }
@@ -770,7 +723,6 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   if (TILES > 1) F = readlane_v3(F, 0);
   wave_lds_fence();
   }
-#endif
   PMAF_SEC(ST, 3);
   scale = (sqn(F) >= C.zf_gt) ? sc : scale;  // norm(F) > 1e-5
   PMAF_SEC(ST, 4);
@@ -803,9 +755,6 @@ __device__ __forceinline__ void path_cost_terms_w64(int lane, const double *path
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   cost_ws = 0.0;
   path_len = 0.0;
-#ifndef PMAF_COST_PREFETCH
-#define PMAF_COST_PREFETCH 1
-#endif
   // (round 3: the next block's six loads are in flight while this block is summed -- the pass was one memory round trip
   // per 64 points in front of each sum)
   V3 q_n = mk(0.0, 0.0, 0.0), qp_n = mk(0.0, 0.0, 0.0);
@@ -817,18 +766,13 @@ __device__ __forceinline__ void path_cost_terms_w64(int lane, const double *path
     q = mk(ld_agent(path + kk * 3), ld_agent(path + kk * 3 + 1), ld_agent(path + kk * 3 + 2));
     qp = mk(ld_agent(path + kp * 3), ld_agent(path + kp * 3 + 1), ld_agent(path + kp * 3 + 2));
   };
-  if (PMAF_COST_PREFETCH) fetch(0, q_n, qp_n);
+  fetch(0, q_n, qp_n);
   for (int base = 0; base < n; base += 64) {
     const int k = base + lane;
     const bool valid = k < n;
     const bool has_seg = valid && (k > 0);
-    V3 q, qp;
-    if (PMAF_COST_PREFETCH) {
-      q = q_n; qp = qp_n;
-      if (base + 64 < n) fetch(base + 64, q_n, qp_n);
-    } else {
-      fetch(base, q, qp);
-    }
+    const V3 q = q_n, qp = qp_n;
+    if (base + 64 < n) fetch(base + 64, q_n, qp_n);
     const double seg = Mth<MATH>::norm(q - qp);
     list[lane] = has_seg ? seg : 0.0;
     wave_lds_fence();

@@ -86,7 +86,6 @@ struct DevView {
   unsigned long long *step_counter;  // [1] agent-steps executed by all rollouts
   unsigned long long *pred_ticks;    // [P][N] rollout duration in wall_clock64() ticks (CfAgent::prediction_time_)
   const double *zsent_lt;            // [P] exact squared-distance boundary of the repel range test
-  int ablate;                        // timing experiments only (PMAF_ABLATE), 0 in production
   int n_simds;                       // SIMDs of the device (4 per CU): a launch of more waves doubles them up
   int prio_slice_log2, prio_younger_of_8;   // wave-per-agent SLICE loop (pmaf_k_w64.hip): slice length in 2^k ticks of the 100 MHz clock, the younger wave's share
   // closest-other table of the rollout-start obstacles (round 3): closest_idx[p][i] = the index the Obstacle /
