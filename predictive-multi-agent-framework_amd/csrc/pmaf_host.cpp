@@ -18,6 +18,7 @@
 #include "pmaf_comm.hpp"
 #include "pmaf_types.hpp"
 #include "pmaf_lpa_model.hpp"
+#include "pmaf_route.hpp"
 
 using namespace pmaf;
 
@@ -56,18 +57,12 @@ static void check_range(const double *v, size_t n, const char *what) {
 struct pmaf_planner {
   DevView D{};
   int device = 0;
-  int lpa = 64;
-  int math = MATH_XACT;        // arithmetic policy of the w64 rollout kernels (pmaf_device.hpp)
-  bool force_generic = false;  // PMAF_FORCE_GENERIC=1: always use the generic k_rollout<LPA>
-  bool w64_slice = false;      // two waves of the wave-per-agent kernel on a SIMD trade issue priority (pmaf_k_w64.hip, SLICE)
-  bool plain_step = false;     // every k_attr != 0 and unit mass: the wave-per-agent kernels' PLAIN step (pmaf_k_w64.hip)
+  // which rollout kernel this handle launches and with what (pmaf_route.hpp): everything the choice depends on, and the
+  // choice -- recomputed by reroute() where an input changes, read everywhere else
+  pmaf_route::Input route_in;
+  pmaf_route::Route route;
   bool blocking_wait = false;  // PMAF_FLAG_BLOCKING_WAIT: pmaf_tick sleeps on an event instead of spinning on the mailbox
-  bool dpp_sum = true;         // w64 kernels: ordered force sum by the DPP chain (M > 20) or LDS batches
-  // W waves per agent (pmaf_k_mw.hip; 0: the wave-per-agent kernels): 61..256 field obstacles, every policy but the compiler-IEEE one
-  // arithmetic, and every wave of the launch with a SIMD to itself (pick_mw)
-  int mw_waves = 0, mw_per = 0, mw_lds_kb = 0;
-  int n_blocks = 0;
-  size_t lds_rollout = 0, lds_manager = 0;
+  size_t lds_manager = 0;
   hipModule_t ext_mod = nullptr;       // pmaf_debug_external_rollout: a rollout kernel loaded from a code object file
   hipFunction_t ext_fn = nullptr;
   hipStream_t stream = nullptr;
@@ -102,13 +97,6 @@ struct pmaf_planner {
     last_live.resize((size_t)D.P * field);
     for (int p = 0; p < D.P; p++) std::memcpy(last_live.data() + p * field, obstacles + p * row, sizeof(double) * field);
     closest_dirty = true;
-  }
-  // the kernels that read the table: the wave-per-agent kernels with several obstacle slots per lane (launch_rollout)
-  // (an external kernel -- pmaf_debug_external_rollout -- is the product kernel's own code and reads the table too)
-  bool uses_closest_table() const {
-    const int M = D.n_obs - 1;
-    const int tiles64 = (M >= 61 && M <= 64) ? 2 : (M + 63) / 64;
-    return lpa == 64 && tiles64 >= 2 && tiles64 <= 4 && !force_generic;
   }
   // host-side clock of the last pmaf_tick calls (pmaf_get_tick_times_us): entry -> both launches enqueued, entry ->
   // set-point on the host; a ring of the newest TICK_RING calls
@@ -288,6 +276,10 @@ static double repel_boundary(double R, double shell) {
   return z;
 }
 
+// The handle's route from its inputs (pmaf_route.hpp). Called where an input changes and nowhere else: pmaf_create,
+// refresh_plain_step, pmaf_debug_external_rollout, and the multi-wave launcher's refusal (dispatch_rollout) -- never per launch.
+static void reroute(pmaf_planner *h) { h->route = pmaf_route::route(h->route_in); }
+
 // Which step the wave-per-agent kernels run (pmaf_k_w64.hip, PLAIN): the one without attractorForce's `k_attr != 0`
 // test and the division by the mass is only valid when every agent's k_attr is non-zero and the agents have unit mass.
 // Decided where the gains / the mass enter the handle: pmaf_create and pmaf_load_state (k_attr == NULL: read them back
@@ -304,55 +296,8 @@ static void refresh_plain_step(pmaf_planner *h, const double *k_attr) {
   for (size_t i = 0; i < PN && plain; i++) plain = (k_attr[i] != 0.0);
   const char *ps = getenv("PMAF_PLAIN_STEP");   // "0": always the general step (tests, timing)
   if (ps && ps[0] == '0') plain = false;
-  h->plain_step = plain;
-}
-
-static int pick_lpa(int N, int P, int M, int n_simds) {
-  // The mapping with the smallest estimated kernel time (pmaf_lpa_model.hpp: a table of measured launch times per
-  // mapping, obstacle slots per lane and waves per SIMD; profiles/r6_lpa_grid.txt). History of the rule it replaces:
-  // rounds 1-4 narrowed the mapping until the launch had <= 2048 waves (the wave per agent wins while every wave has a SIMD
-  // to itself and still at two per SIMD; the group kernels run best at two per SIMD); round 5 added "never more than two
-  // obstacle slots per lane in a narrower mapping" (profiles/r5_lpa_rule.txt: the three- / four-slot group bodies and the
-  // generic kernel cost more than another round of waves: 128 obstacles x 4096 agents 1882 -> 1149 us); round 6 measured
-  // the whole plane and found that rule 20 ... 31 % off in three regions (header of pmaf_lpa_model.hpp). BASELINE's
-  // configurations keep their mappings: C1-C4 the wave per agent, C5 x 8 on one GPU 16 lanes, x 4 32 lanes, x 2 / x 1 64.
-  int lpa = pmaf_lpa::pick(N, P, M, n_simds);
-  // known-flag bitmask holds 64 tiles per lane
-  while ((M + lpa - 1) / lpa > 64 && lpa < 64) lpa *= 2;
-  return lpa;
-}
-
-// W waves per agent with <= 61 obstacles each (pmaf_k_mw.hip) instead of 2 / 4 obstacle slots per lane of ONE wave:
-// the per-obstacle part of the step runs on W SIMDs at once. Only while the launch leaves every BLOCK a CU of its own
-// (N P <= CUs of the device) -- beyond that the multi-slot kernels' single wave per agent wins back.
-// PMAF_MW=0 / 2 / 3 / 4: off / that many waves (tests, timing); PMAF_MW_PER: obstacles per wave (default: even split).
-static void pick_mw(pmaf_planner *h, int N, int P, int M) {
-  h->mw_waves = 0; h->mw_per = 0;
-  if (h->lpa != 64 || h->force_generic || h->math == MATH_IEEE) return;
-  if (M < 61 || M > 4 * 64) return;
-  // as few waves as hold the obstacles at 64 per wave (every wave more costs ~0.24 us per step: profiles/r4_ab_mw.txt);
-  // at <= 61 per wave lanes 61..63 stay free for the tail's riders and the sweep's norms ride along (pmaf_k_mw.hip)
-  int waves = (M + 63) / 64;
-  if (waves < 2) waves = 2;
-  const char *e = getenv("PMAF_MW");
-  if (e && e[0]) {
-    const int f = atoi(e);
-    if (f == 0) return;
-    if (f >= waves && f <= 4) waves = f;
-  }
-  // ONE block per CU (pmaf_k_mw.hip's launcher enforces it through the LDS request). Rounds 4's rule let two two-wave
-  // blocks share a CU (N P <= 2 CUs); measured in round 5 (profiles/r5_mw_rule_sweep.txt, 300 steps, kernel us per launch):
-  //   128 obstacles: 256 agents split 536 / one-wave 578, 288 ... 512 agents split 710 ... 716 / one-wave 601
-  //   100 obstacles: 256 agents 492 / 550, 384 ... 512 agents 649 ... 652 / 574;   64 obstacles: 445 / 515, 616 ... 621 / 540
-  // -- as soon as ONE CU holds two blocks (their four waves contend for the CU's LDS pipe at the per-step hand-off) the
-  // launch is 18 % slower than the two-slot one-wave kernel, so the split kernel is kept to launches with a CU per block.
-  const long cus = h->D.n_simds / 4;
-  if ((long)N * P > cus) return;
-  { const char *lk = getenv("PMAF_MW_LDS_KB"); h->mw_lds_kb = lk ? atoi(lk) : 0; }   // timing experiments
-  int per = (M + waves - 1) / waves;
-  const char *pe = getenv("PMAF_MW_PER");
-  if (pe && atoi(pe) >= per && atoi(pe) <= 64) per = atoi(pe);
-  h->mw_waves = waves; h->mw_per = per;
+  h->route_in.plain_step = plain;
+  reroute(h);
 }
 
 // fold finished rollout event pairs (oldest first) into the stats; all=true
@@ -372,14 +317,35 @@ static void drain_events(pmaf_planner *h, bool all) {
   h->ev_inflight.erase(h->ev_inflight.begin(), h->ev_inflight.begin() + (long)done);
 }
 
-// Does this handle's wave-per-agent launch run the priority-slicing loop (k_rollout_w64_sliced)? ONE predicate for the launch and
-// for pmaf_get_priority_slices: more one-slot waves than SIMDs and at most two per SIMD, the kernel variants that exist with
-// the loop (DPP sum, PLAIN step, strict or contracted arithmetic), and none of the routes that bypass k_rollout_w64.
-static bool w64_sliced(const pmaf_planner *h) {
-  const int M = h->D.n_obs - 1;
-  const long waves = (long)h->D.N * h->D.P;
-  return h->w64_slice && h->lpa == 64 && !h->force_generic && !h->mw_waves && !h->ext_fn && M <= 60 && h->dpp_sum && h->plain_step &&
-         (h->math == MATH_XACT || h->math == MATH_FMA) && waves > h->D.n_simds && waves <= 2L * h->D.n_simds;
+// The launch the handle's route names; only forwards the route's fields.
+static bool dispatch_rollout(pmaf_planner *h, hipEvent_t e0, hipEvent_t e1) {
+  const pmaf_route::Route &r = h->route;
+  switch (r.family) {
+    case pmaf_route::EXTERNAL: {
+      // (measurement tooling, tools/slackprof; events as marker packets around it)
+      void *args[] = {(void *)&h->D, (void *)&h->cp};
+      if (e0) HIP_CHECK(hipEventRecord(e0, h->stream));
+      HIP_CHECK(hipModuleLaunchKernel(h->ext_fn, (unsigned)h->D.N, (unsigned)h->D.P, 1, 64, 1, 1, (unsigned)r.lds_rollout,
+                                      h->stream, args, nullptr));
+      if (e1) HIP_CHECK(hipEventRecord(e1, h->stream));
+      return true;
+    }
+    case pmaf_route::MULTI_WAVE:
+      if (pmaf_k_launch_mw(h->D, h->cp, r.waves, r.per, r.math, r.plain, r.mw_lds_kb, h->stream, e0, e1)) return true;
+      // (the split kernel refused the launch -- its 72 / 96 KB LDS opt-in failed on this device, or a bad PMAF_MW_LDS_KB:
+      // the one-wave kernels serve every such population, bit for bit the same; pmaf_get_waves_per_agent reports 1 from now on)
+      (void)hipGetLastError();
+      h->route_in.mw_refused = true;
+      reroute(h);
+      return dispatch_rollout(h, e0, e1);
+    case pmaf_route::WAVE_PER_AGENT:
+      return pmaf_k_launch_w64(h->D, h->cp, r.tiles, r.math, r.dpp_sum, r.plain, r.lds_rollout, h->stream, e0, e1, r.sliced);
+    case pmaf_route::GROUP:
+      return pmaf_k_launch_grp(h->D, h->cp, r.lpa, r.tiles, r.math, r.n_blocks, r.lds_rollout, h->stream, e0, e1);
+    case pmaf_route::GENERIC:
+      break;
+  }
+  return pmaf_k_launch_generic(h->D, h->cp, r.lpa, r.n_blocks, r.lds_rollout, h->stream, e0, e1);
 }
 
 static void launch_rollout(pmaf_planner *h) {
@@ -400,36 +366,7 @@ static void launch_rollout(pmaf_planner *h) {
   // with a communicator attached the rollout writes the OTHER path buffer: the exchange of the selection just made
   // may still be packing the path it scored (the getters follow D.paths)
   if (h->x.c) h->D.paths = (h->D.paths == h->x.paths_a) ? h->x.paths_b : h->x.paths_a;
-  // (the one-slot kernel keeps lanes 61-63 for the goal and the two speed limits and lane 60 for the repulsive obstacle:
-  // 61-64 obstacles go to the split / two-slot kernels)
-  const int M = h->D.n_obs - 1;
-  const int tiles64 = (M >= 61 && M <= 64) ? 2 : (M + 63) / 64;
-  bool ok;
-  if (h->ext_fn) {
-    // measurement tooling (tools/slackprof): the same launch with a kernel out of an external code object -- the
-    // product kernel's own assembly with delay instructions inserted; events as marker packets around it
-    void *args[] = {(void *)&h->D, (void *)&h->cp};
-    if (e0) HIP_CHECK(hipEventRecord(e0, h->stream));
-    HIP_CHECK(hipModuleLaunchKernel(h->ext_fn, (unsigned)h->D.N, (unsigned)h->D.P, 1, 64, 1, 1, (unsigned)h->lds_rollout,
-                                    h->stream, args, nullptr));
-    if (e1) HIP_CHECK(hipEventRecord(e1, h->stream));
-    ok = true;
-  } else if (h->mw_waves &&
-             pmaf_k_launch_mw(h->D, h->cp, h->mw_waves, h->mw_per, h->math, h->plain_step, h->mw_lds_kb, h->stream, e0, e1))
-    ok = true;
-  else if (h->lpa == 64 && tiles64 <= 4 && !h->force_generic) {
-    // (the split kernel refused the launch -- its 72 / 96 KB LDS opt-in failed on this device, or a bad PMAF_MW_LDS_KB:
-    // the one-wave kernels serve every such population, bit for bit the same; pmaf_get_waves_per_agent reports 1 from now on)
-    if (h->mw_waves) { (void)hipGetLastError(); h->mw_waves = 0; h->mw_per = 0; }
-    // ordered force sum: the DPP chain (h->dpp_sum, see pmaf_create), LDS batches on request (pmaf_rollout_w64.hpp)
-    const bool slice = w64_sliced(h);   // two one-slot waves per SIMD: the priority-slicing loop (pmaf_k_w64.hip, SLICE)
-    ok = pmaf_k_launch_w64(h->D, h->cp, tiles64, h->math, h->dpp_sum, h->plain_step, h->lds_rollout, h->stream, e0, e1, slice);
-  } else if (!h->force_generic && (h->lpa == 32 || h->lpa == 16 || h->lpa == 8) && (M + h->lpa - 1) / h->lpa <= 4)
-    // (policy 1, the plain fast arithmetic, exists for the w64 kernels only)
-    ok = pmaf_k_launch_grp(h->D, h->cp, h->lpa, (M + h->lpa - 1) / h->lpa, h->math == MATH_FAST ? MATH_XACT : h->math,
-                           h->n_blocks, h->lds_rollout, h->stream, e0, e1);
-  else
-    ok = pmaf_k_launch_generic(h->D, h->cp, h->lpa, h->n_blocks, h->lds_rollout, h->stream, e0, e1);
+  const bool ok = dispatch_rollout(h, e0, e1);
   if (!ok) fail(PMAF_ERR_INVALID, "no rollout kernel for this lanes_per_agent / obstacle count in this build");
   HIP_CHECK(hipGetLastError());
   h->launches++;
@@ -514,8 +451,8 @@ static void launch_manager(pmaf_planner *h, const ManagerArgs &A0, hipEvent_t do
     }
   }
   if (A.do_reset) h->paths_gen++;
-  if (A.do_reset && h->uses_closest_table()) { A.compute_closest = h->closest_dirty ? 1 : 0; h->closest_dirty = false; }
-  A.tuned_real_step = (h->math == MATH_XACT && !h->force_generic) ? 1 : 0;
+  if (A.do_reset && h->route.closest_table) { A.compute_closest = h->closest_dirty ? 1 : 0; h->closest_dirty = false; }
+  A.tuned_real_step = h->route.tuned_real_step ? 1 : 0;
   pmaf_k_launch_manager(h->D, h->cp, A, h->lds_manager, h->stream, done);
   HIP_CHECK(hipGetLastError());
   if (hand_over_position) h->real_pos_pending = false;   // (only once the launch that reads it is in the stream)
@@ -853,7 +790,9 @@ int pmaf_create(const pmaf_params *prm, pmaf_planner **out) {
     D.C.zf_gt = sq_gt(1e-5); D.C.zacc_gt = sq_gt(13.0); D.C.zinit_lt = sq_ge(0.2);
     D.C.zvhalf_lt = sq_ge(0.5 * prm->velocity_max);
     D.C.zv09_lt = sq_ge(prm->velocity_max - 0.1 * prm->velocity_max);
-    h->math = (prm->flags & PMAF_FLAG_CONTRACTED) ? MATH_FMA : (prm->flags & PMAF_FLAG_FAST_MATH) ? MATH_FAST
+    pmaf_route::Input &ri = h->route_in;
+    ri.N = N; ri.P = P; ri.M = M; ri.lanes_request = lp;
+    ri.math = (prm->flags & PMAF_FLAG_CONTRACTED) ? MATH_FMA : (prm->flags & PMAF_FLAG_FAST_MATH) ? MATH_FAST
               : (prm->flags & PMAF_FLAG_IEEE_SEQUENCES) ? MATH_IEEE : MATH_XACT;
     h->blocking_wait = (prm->flags & PMAF_FLAG_BLOCKING_WAIT) != 0;
     {
@@ -861,50 +800,29 @@ int pmaf_create(const pmaf_params *prm, pmaf_planner **out) {
       HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
       D.n_simds = 4 * (cus > 0 ? cus : 256);
     }
-    h->lpa = lp ? lp : pick_lpa(N, P, M, D.n_simds);
-    { const char *fg = getenv("PMAF_FORCE_GENERIC"); h->force_generic = fg && fg[0] == '1'; }
-    // Two waves of the wave-per-agent kernel on one SIMD (1 025 ... 2 048 agents in the handle) trade issue priority in slices
-    // of the wall clock so that both finish together (pmaf_k_w64.hip, SLICE; pmaf_get_priority_slices). tools/slicesweep.py,
-    // profiles/r6_slice_sweep.txt, kernel us per launch without -> with (slices of 2^9 ticks = 5.1 us, the younger wave 5 of 8):
-    //   32 obstacles: 1 280 agents 347 -> 326, 1 536: 359 -> 334, 2 048: 381 -> 364;  9 x 2 048: 376 -> 362;  60 x 2 048: 383 -> 370;
-    //   BASELINE C5, two scenes in the handle (its per-GPU load at 4 GPUs): 386 -> 372.  Settings 2^8 ... 2^10 x 4 ... 6 of 8: within 2 %.
-    // The arithmetic and its order are the same instructions: bit-identical results (tests/test_parity_gpu.py runs these shapes).
-    // PMAF_W64_SLICE=0|1, PMAF_W64_SLICE_LOG2, PMAF_W64_SLICE_YOUNGER in the environment: timing experiments.
-    { const char *e = getenv("PMAF_W64_SLICE"); h->w64_slice = e ? (e[0] == '1') : true; }
+    ri.n_simds = D.n_simds;
+    // the route's switches in the environment (tests, timing experiments; what each does: pmaf_route.hpp)
+    { const char *fg = getenv("PMAF_FORCE_GENERIC"); ri.force_generic = fg && fg[0] == '1'; }
+    { const char *e = getenv("PMAF_W64_SLICE"); ri.w64_slice = e ? (e[0] == '1') : true; }
+    { const char *ds = getenv("PMAF_SUM"); ri.dpp_sum = (ds && ds[0]) ? (ds[0] == 'd') : true; }  // "dpp" / "lds"
+    { const char *e = getenv("PMAF_MW"); ri.mw = (e && e[0]) ? atoi(e) : -1; }
+    { const char *e = getenv("PMAF_MW_PER"); ri.mw_per = e ? atoi(e) : 0; }
+    { const char *e = getenv("PMAF_MW_LDS_KB"); ri.mw_lds_kb = e ? atoi(e) : 0; }
+    reroute(h);   // (plain_step still false: refresh_plain_step below, once the gains are in)
+    // the priority-slicing loop's settings (PMAF_W64_SLICE_LOG2, PMAF_W64_SLICE_YOUNGER: timing experiments)
     { const char *e = getenv("PMAF_W64_SLICE_LOG2"); D.prio_slice_log2 = std::min(20, std::max(4, e ? atoi(e) : 9)); }       // (a shift count on the device)
     { const char *e = getenv("PMAF_W64_SLICE_YOUNGER"); D.prio_younger_of_8 = std::min(7, std::max(1, e ? atoi(e) : 5)); }
     { const char *to = getenv("PMAF_EXCHANGE_TIMEOUT_S"); if (to && atof(to) > 0.0) h->exchange_timeout_s = atof(to); }
     { const char *to = getenv("PMAF_TICK_TIMEOUT_S"); if (to && atof(to) > 0.0) h->tick_timeout_s = atof(to); }
-    // ordered force sum: the DPP chain for every obstacle count (round 3: with the first chunk's accumulates fused and
-    // interleaved with the scaling chain it also wins for short lists -- C1, nine obstacles: 121.3 -> 111.8 us; rounds 1-2
-    // switched to LDS batches below 21 obstacles). PMAF_SUM=lds selects the LDS-batch kernels (tests, timing).
-    h->dpp_sum = true;
-    { const char *ds = getenv("PMAF_SUM"); if (ds && ds[0]) h->dpp_sum = (ds[0] == 'd'); }  // "dpp" / "lds": tests, timing
-    pick_mw(h, N, P, M);
-    REQUIRE((M + h->lpa - 1) / h->lpa <= 64, "pmaf_create: too many obstacles for this lanes_per_agent (need M <= 64*lanes_per_agent)");
-    h->n_blocks = (N * h->lpa + 63) / 64;
-    {
-      // obstacle table + known flags, then (w64 kernels) the per-step list of
-      // circular-field terms: 64 * TILES entries of 4 doubles
-      size_t off = 7 * (size_t)n_obs + ((size_t)n_obs + 1) / 2;
-      off += off & 1;
-      // w64: (64 * TILES + 8 padding + 64 scratch) entries; groups: 64 * TILES + one zero entry per group (<= 8).
-      // TILES as dispatched (launch_rollout), never below 2: with the four-slot size a one-wave block of 129 obstacles
-      // asks for 18.5 KB + the kernel's 2.1 KB of static LDS (exp's table) -- over the 20 KB that let eight blocks
-      // share a CU, and 2048+ agents x 128 obstacles ran at 7/8 occupancy with a second round of blocks (+45 %).
-      const int slots = (M + h->lpa - 1) / h->lpa;
-      const bool narrow = h->lpa == 64 || h->lpa == 32 || h->lpa == 16 || h->lpa == 8;
-      const int tiles = (narrow && !h->force_generic && slots <= 2) ? 2 : 4;
-      h->lds_rollout = sizeof(double) * (off + (size_t)pmaf_list_area_doubles(tiles) + 8 * 4);
-    }
+    REQUIRE((M + h->route.lpa - 1) / h->route.lpa <= 64, "pmaf_create: too many obstacles for this lanes_per_agent (need M <= 64*lanes_per_agent)");
     // table | known flags | costs | the tuned real step's list (64 * 4 + 8 + 64 entries of 4 doubles)
     // (+ 2: the wave-minimum cell of circ_and_scale_w64 behind the list)
     h->lds_manager = sizeof(double) * (7 * (size_t)n_obs + ((size_t)n_obs + 1) / 2 + (size_t)N + 1 + (size_t)pmaf_list_area_doubles(4) + 2);
-    REQUIRE(h->lds_rollout <= 160 * 1024, "pmaf_create: obstacle table does not fit in LDS");
+    REQUIRE(h->route.lds_rollout <= 160 * 1024, "pmaf_create: obstacle table does not fit in LDS");
     REQUIRE(h->lds_manager <= 160 * 1024,
             "pmaf_create: n_agents + obstacle table exceed the manager kernel's LDS budget (160 KB: 8 B per agent, 60 B per obstacle)");
     // dynamic LDS beyond the 64 KB default needs the per-function opt-in
-    HIP_CHECK(pmaf_k_set_lds_limits(h->lds_manager, h->lds_rollout));
+    HIP_CHECK(pmaf_k_set_lds_limits(h->lds_manager, h->route.lds_rollout));
 
     size_t PN = (size_t)P * N;
     double *goal = h->dalloc<double>(P * 3);
@@ -1387,7 +1305,7 @@ static void plan_steps(pmaf_planner *h, const double *obstacles, double dt, int 
     HIP_CHECK(hipMemsetAsync(h->d_plan_calls, 0, sizeof(int32_t) * D.P, h->stream));
   }
   h->paths_gen++;
-  if (!pmaf_k_launch_plan_steps(D, A, h->lpa, h->n_blocks, h->lds_rollout, h->stream)) fail(PMAF_ERR_INVALID, "bad lanes_per_agent");
+  if (!pmaf_k_launch_plan_steps(D, A, h->route.lpa, h->route.n_blocks, h->route.lds_rollout, h->stream)) fail(PMAF_ERR_INVALID, "bad lanes_per_agent");
   HIP_CHECK(hipGetLastError());
   sync(h);
   if (agent_id && calls) h->download(calls, h->d_plan_calls, D.P);
@@ -2609,36 +2527,41 @@ int pmaf_debug_external_rollout(pmaf_planner *h, const char *code_object_path, c
     h->use_device();
     sync(h);
     if (h->ext_mod) { (void)hipModuleUnload(h->ext_mod); h->ext_mod = nullptr; h->ext_fn = nullptr; }
+    h->route_in.external = false;
+    reroute(h);
     if (!code_object_path) return;
     REQUIRE(kernel_name, "pmaf_debug_external_rollout: kernel name required");
-    REQUIRE(h->lpa == 64, "pmaf_debug_external_rollout: wave-per-agent launches only (grid N x P, one wave per block)");
+    REQUIRE(h->route.lpa == 64, "pmaf_debug_external_rollout: wave-per-agent launches only (grid N x P, one wave per block)");
     HIP_CHECK(hipModuleLoad(&h->ext_mod, code_object_path));
     HIP_CHECK(hipModuleGetFunction(&h->ext_fn, h->ext_mod, kernel_name));
+    h->route_in.external = true;
+    reroute(h);
   });
 }
 
 int pmaf_get_launch_config(pmaf_planner *h, int32_t *lanes_per_agent, int32_t *n_blocks, int32_t *lds_bytes) {
   return guarded([&] {
     REQUIRE(h, "pmaf_get_launch_config: NULL handle");
-    if (lanes_per_agent) *lanes_per_agent = h->lpa;
-    if (n_blocks) *n_blocks = h->n_blocks * h->D.P;
-    if (lds_bytes) *lds_bytes = (int32_t)h->lds_rollout;
+    // (the one-wave figures for every handle: a MULTI_WAVE route's launcher asks for 96 KB on a grid of N x P itself
+    // -- pmaf_k_mw.hip -- and this getter has always reported the one-wave kernel's blocks and bytes beside it)
+    if (lanes_per_agent) *lanes_per_agent = h->route.lpa;
+    if (n_blocks) *n_blocks = h->route.n_blocks * h->D.P;
+    if (lds_bytes) *lds_bytes = (int32_t)h->route.lds_rollout;
   });
 }
 
 int pmaf_get_waves_per_agent(pmaf_planner *h, int32_t *waves_per_agent, int32_t *obstacles_per_wave) {
   return guarded([&] {
     REQUIRE(h, "pmaf_get_waves_per_agent: NULL handle");
-    if (waves_per_agent) *waves_per_agent = h->mw_waves ? h->mw_waves : 1;
-    if (obstacles_per_wave) *obstacles_per_wave = h->mw_waves ? h->mw_per : h->D.n_obs - 1;
+    if (waves_per_agent) *waves_per_agent = h->route.waves;
+    if (obstacles_per_wave) *obstacles_per_wave = h->route.per;
   });
 }
 
 int pmaf_get_priority_slices(pmaf_planner *h, int32_t *enabled, int32_t *slice_ticks, int32_t *younger_of_8) {
   return guarded([&] {
     REQUIRE(h, "pmaf_get_priority_slices: NULL handle");
-    const bool on = w64_sliced(h);
-    if (enabled) *enabled = on ? 1 : 0;
+    if (enabled) *enabled = h->route.sliced ? 1 : 0;
     if (slice_ticks) *slice_ticks = 1 << h->D.prio_slice_log2;
     if (younger_of_8) *younger_of_8 = h->D.prio_younger_of_8;
   });
@@ -2646,7 +2569,7 @@ int pmaf_get_priority_slices(pmaf_planner *h, int32_t *enabled, int32_t *slice_t
 
 int32_t pmaf_pick_lanes_per_agent(int32_t n_agents, int32_t n_populations, int32_t n_field_obstacles, int32_t n_simds) {
   if (n_agents < 1 || n_populations < 1 || n_field_obstacles < 0) return 0;
-  return pick_lpa(n_agents, n_populations, n_field_obstacles, n_simds > 0 ? n_simds : 1024);
+  return pmaf_route::pick_lpa(n_agents, n_populations, n_field_obstacles, n_simds > 0 ? n_simds : 1024);
 }
 
 double pmaf_estimate_rollout_us(int32_t lanes_per_agent, int32_t n_agents, int32_t n_populations, int32_t n_field_obstacles,

@@ -47,7 +47,7 @@ static const Row kRows[] = {
   {8, 2, 9, {524, 739, 1190, 1400}, 330, 16, {587, 815, 1310, 1550}, 360},
 };
 
-// obstacle slots per lane of the kernel that mapping dispatches (launch_rollout): the wave per agent keeps lanes 60 ... 63
+// obstacle slots per lane of the kernel that mapping dispatches (pmaf_route.hpp, Route::tiles): the wave per agent keeps lanes 60 ... 63
 // for the tail's riders, so its one-slot kernel ends at 60 obstacles; 129 ... 256 run its four-slot kernel
 static inline int slots_of(int lpa, int M) {
   if (lpa == 64) return M <= 60 ? 1 : M <= 128 ? 2 : 4;

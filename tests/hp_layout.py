@@ -6,8 +6,8 @@ indices, every one of them decided by the high-precision reference (tests/hp_ref
 
 Where an obstacle index lives (read from csrc/; M field obstacles, the trailing repulsive one is not in these sweeps):
   k_rollout_w64 (pmaf_k_w64.hip, pmaf_rollout_w64.hpp)   obstacle i in lane i % 64, slot i / 64; one slot for M <= 60,
-                                                         2 slots for M = 61..128, 3 to 192, 4 to 256 (pmaf_host.cpp
-                                                         launch_rollout: tiles64)
+                                                         2 slots for M = 61..128, 3 to 192, 4 to 256 (pmaf_route.hpp
+                                                         route: slots64)
   k_rollout_mw (pmaf_k_mw.hip, base = w * per)           W = max(2, ceil(M / 64)) waves (PMAF_MW raises it, up to 4),
                                                          per = ceil(M / W); obstacle i in wave i / per, lane i % per
   k_rollout_grp / generic k_rollout (i = t * LPA + sub)  obstacle i in lane i % LPA of the agent's group, slot i / LPA;

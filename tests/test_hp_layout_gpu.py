@@ -6,7 +6,7 @@ property); the term-list cases (family C) also run under the contracted policy.
 
 The nearest other obstacle of the latch (family B) is answered by two code paths, and nothing in the C-ABI reports
 which one ran, so it follows from the inputs: with every field obstacle at rest, k_manager writes the closest-other table
-at the reset that carries the new list (pmaf_host.cpp: closest_dirty, uses_closest_table; pmaf_k_misc.hip: closest_ok =
+at the reset that carries the new list (pmaf_host.cpp: closest_dirty; pmaf_route.hpp: closest_table; pmaf_k_misc.hip: closest_ok =
 1 only if no velocity component is non-zero), and k_rollout_w64 with 2 .. 4 slots and k_rollout_mw read it; with one far
 obstacle moving, closest_ok = 0 and the same kernels run their cooperative scans. The one-slot kernel, k_rollout_grp and
 the generic kernel always scan. Every case is run both ways.

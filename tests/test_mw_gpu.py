@@ -61,6 +61,40 @@ def test_one_wave_kernels_on_request_and_beyond_one_wave_per_simd(pmaf, oracle, 
     hip.close()
 
 
+def test_refused_split_launch_falls_back_to_the_one_wave_kernels(pmaf, scenes, monkeypatch):
+    """the multi-wave launcher refuses the launch (here: an LDS opt-in beyond the CU's 160 KB, which hipFuncSetAttribute
+    rejects -- an error return, nothing reaches the device): the same tick runs the one-wave kernels instead, bit for bit
+    what PMAF_MW=0 gives, and the handle reports one wave per agent from then on (csrc/pmaf_route.hpp: mw_refused)"""
+    sc = scenes.synthetic_scene(6, 8, 70, 7, 5)                  # one agent per heuristic, two waves of 35 obstacles
+
+    def run(env):
+        for k in ("PMAF_MW", "PMAF_MW_LDS_KB"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        hip = pmaf.PmafPlanner(sc, device=0, mgr_init_pos=sc["start"])
+        hip.set_initial_position(sc["start"])
+        cfgs = [hip.launch_config()]
+        for _ in range(2):
+            hip.tick(sc["obstacles"], sc["dt"], sc["cost_gains"], sc["ws_limits"])
+            hip.stop()
+            cfgs.append(hip.launch_config())
+        out = (hip.paths(), hip.costs())
+        hip.close()
+        return cfgs, out
+
+    cfgs, refused = run({"PMAF_MW_LDS_KB": "200"})
+    assert cfgs[0]["waves_per_agent"] == 2                       # before the first launch: the split the route chose
+    assert [(c["waves_per_agent"], c["obstacles_per_wave"]) for c in cfgs[1:]] == [(1, 70), (1, 70)]
+    cfgs0, one_wave = run({"PMAF_MW": "0"})
+    assert [c["waves_per_agent"] for c in cfgs0] == [1, 1, 1]
+    assert {k: v for k, v in cfgs[1].items()} == cfgs0[1]
+    (pa, na), (pb, nb) = refused[0], one_wave[0]
+    np.testing.assert_array_equal(na, nb)
+    assert np.array_equal(pa, pb, equal_nan=True)
+    assert np.array_equal(np.asarray(refused[1]), np.asarray(one_wave[1]), equal_nan=True)
+
+
 def test_signed_zeros_gate_runs_and_early_stops(pmaf, oracle, scenes):
     """-0.0 coordinates / velocity components of obstacles at rest (the mirror's second buffer holds the positions
     after ONE predictObstacles), a start inside the gate for many steps (no exchange while it is closed: the buffers'

@@ -1292,7 +1292,7 @@ def test_synchronous_stepping_api_matches_oracle(pmaf, oracle, scenes, lpa):
     # ... and the band between one and two waves per SIMD of the wave per agent, where nothing changes (profiles/r6_lpa_band.txt)
     (1280, 1, 32, 64), (2048, 1, 32, 64), (1024, 2, 32, 64), (1792, 1, 9, 64), (2048, 1, 60, 64)])
 def test_narrower_mappings_are_chosen_by_the_measured_table(pmaf, oracle, scenes, n, p, m, want):
-    """pick_lpa: the mapping with the smallest estimated launch time (csrc/pmaf_lpa_model.hpp, a table of measured times;
+    """pick_lpa (csrc/pmaf_route.hpp): the mapping with the smallest estimated launch time (csrc/pmaf_lpa_model.hpp, a table of measured times;
     round 5's structural rule -- at most two obstacle slots per lane in a narrower mapping -- is what it offers from).
     Parity of the populations whose mapping changed in round 6, of round 5's, and of neighbours whose mapping stayed:
     every path point, cost and index against the oracle, tolerance 0, P populations against P oracles."""

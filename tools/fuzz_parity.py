@@ -21,7 +21,7 @@ for trial in range(n_trials):
     H = int(rng.integers(5, 160)); dyn = bool(rng.integers(0, 2))
     if rng.integers(0, 25) == 0:   # a large population (multi-block launches of the group kernels), short horizon
         N = int(rng.integers(200, 1500)); H = int(rng.integers(5, 30)); M = int(rng.choice([3, 17, 32, 40]))
-    if MANY:   # PMAF_FUZZ_MANY=1 (round 6): every trial is a many-agent population -- the shapes pick_lpa's measured table decides
+    if MANY:   # PMAF_FUZZ_MANY=1 (round 6): every trial is a many-agent population -- the shapes pick_lpa's (csrc/pmaf_route.hpp) measured table decides
         # (16 / 32 / 64 lanes per agent, the wave per agent's priority-slicing loop between 1 025 and 2 048 agents), short horizons
         N = int(rng.choice([rng.integers(1025, 2049), rng.integers(2049, 4600), rng.integers(900, 1100)]))
         H = int(rng.integers(4, 22)); M = int(rng.choice([0, 3, 9, 16, 17, 32, 33, 48, 59, 60, 61, 64, 65, 100]))

@@ -1,5 +1,5 @@
 """kernel us per launch over lanes-per-agent mappings for P populations x N agents x M field obstacles in ONE handle
-(round 6: the 1 025 ... 2 048-wave band of pick_lpa, i.e. between one and two waves per SIMD of the wave-per-agent kernel).
+(round 6: the 1 025 ... 2 048-wave band of pick_lpa (csrc/pmaf_route.hpp), i.e. between one and two waves per SIMD of the wave-per-agent kernel).
 usage: python tools/lpaband.py M:N:P:lpa,lpa,... [...]   (lpa 0 = the library's choice; H from the environment, default 200)
 Interleaved repeats (REPS, default 3), the median per mapping is printed: boxes differ by +- 2 %, runs on one box by +- 0.3 %."""
 import os, sys

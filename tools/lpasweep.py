@@ -1,5 +1,5 @@
 """kernel us per launch over lanes-per-agent mappings for synthetic populations (many agents x many obstacles):
-which mapping pick_lpa should choose. usage: python tools/lpasweep.py M:N:lpa,lpa,... [...]   (lpa 0 = the library's choice)"""
+which mapping pick_lpa (csrc/pmaf_route.hpp) should choose. usage: python tools/lpasweep.py M:N:lpa,lpa,... [...]   (lpa 0 = the library's choice)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
