@@ -687,7 +687,12 @@ int pmaf_debug_withhold_mailbox(pmaf_planner *h, int32_t enable);
  * 14..17: the opt-in fast policy's operations, which carry an error bound
  * instead: 14: a / b through its refined reciprocal, 15: its sqrt(a), 16: the
  * reciprocal root y ~ 1 / sqrt(b) its norm sequence shares, 17: a / sqrt(b) as
- * the product a * y that replaces the division by a norm. */
+ * the product a * y that replaces the division by a norm.
+ * 18: the default policy's refined reciprocal of b by itself (a is ignored):
+ * RN(1 / b); 19: the reciprocal of the double sqrt(b), taken from the root's own
+ * iteration as the kernels' norms take it (a is ignored; b positive and
+ * finite); 20: a / sqrt(b) through that reciprocal and the fixup-free
+ * division. Compared bitwise like ops 5..13 (tests/test_rcp_bias_gpu.py). */
 int pmaf_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out);
 
 #ifdef __cplusplus

@@ -12,7 +12,7 @@
 #                        pmaf_cross_audit.hpp with the cross audit), a unit of its own so that the other units'
 #                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
 #                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
-#   pmaf_k_dbgmath.hip   ops 13..17 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
+#   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
 #   pmaf_shard.cpp       communicators + the winner-record exchange (RCCL / host-callback)

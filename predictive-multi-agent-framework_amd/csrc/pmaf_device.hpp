@@ -103,8 +103,10 @@ __device__ __forceinline__ double smin(double a, double b) { return (b < a) ? b 
 //                exponents over +-250, every divisor mantissa 2^53 - k and
 //                2^52 + k for odd k < 4096 among them: bit equality, sign of
 //                zero included. (That found rcp_refined, below, 1 ulp off for
-//                three divisor mantissas; with its third step the policy is
-//                correctly rounded there where the compiler's expansion is not.)
+//                three divisor mantissas; with an exact last Newton step behind
+//                a cubic step biased upwards by 2^-54 it returns RN(1 / b), and
+//                the policy is correctly rounded there where the compiler's
+//                expansion is not: tests/test_rcp_bias_gpu.py, op 18.)
 //                Outside +-250 (denormal-scale operands) results stay accurate to
 //                rounding error but are not guaranteed bit-identical.
 // MATH_FAST (1)  opt-in (PMAF_FLAG_FAST_MATH): v_rcp_f64 / v_rsq_f64 seeds
@@ -156,25 +158,15 @@ template <> struct Mth<MATH_IEEE> {
   static __device__ __forceinline__ V3 normalized(V3 a) { return pmaf::normalized(a); }
 };
 template <> struct Mth<MATH_XACT> {
-  static __device__ __forceinline__ double sqrt(double z) {
+  // The Goldschmidt iteration, once: the root g WITHOUT the zero / infinity select, and y2 = y (1 + r) ~ 1 / g to
+  // 2^-47 out of the same iteration (one independent FMA beside the h update; dead code where the caller drops it):
+  // the seed of rcp_seeded
+  static __device__ __forceinline__ double sqrt_seed(double z, double &y2) {
     double y = __builtin_amdgcn_rsq(z);
     double g = z * y, h = 0.5 * y;
     double r = __builtin_fma(-h, g, 0.5);
     g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, z);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, z);
-    g = __builtin_fma(d, h, g);
-    return (z == 0.0 || z == __builtin_huge_val()) ? z : g;  // sqrt(+-0) = +-0, sqrt(inf) = inf
-  }
-  // sqrt(z) for a z that is known to be positive and finite, or whose root is discarded otherwise (the caller's
-  // select says so): the same iteration without the zero / infinity select (3 instructions)
-  static __device__ __forceinline__ double sqrt_pos(double z) {
-    double y = __builtin_amdgcn_rsq(z);
-    double g = z * y, h = 0.5 * y;
-    double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
+    y2 = __builtin_fma(y, r, y);
     h = __builtin_fma(h, r, h);
     double d = __builtin_fma(-g, g, z);
     g = __builtin_fma(d, h, g);
@@ -182,25 +174,60 @@ template <> struct Mth<MATH_XACT> {
     g = __builtin_fma(d, h, g);
     return g;
   }
+  static __device__ __forceinline__ double zinf(double z, double g) { return (z == 0.0 || z == __builtin_huge_val()) ? z : g; }
+  // sqrt(z) for a z that is known to be positive and finite, or whose root is discarded otherwise (the caller's
+  // select says so): the iteration without the zero / infinity select (3 instructions)
+  static __device__ __forceinline__ double sqrt_pos(double z) { double y2; return sqrt_seed(z, y2); }
+  static __device__ __forceinline__ double sqrt(double z) { return zinf(z, sqrt_pos(z)); }  // sqrt(+-0) = +-0, sqrt(inf) = inf
+  // RN(1 / s) from a seed within 2^-40 of it: the biased step and the exact last step of rcp_refined, no v_rcp_f64.
+  // (The historical `2h + one step` shortcut made right: it lacked the exact last step and the all-ones rule, which the
+  // bias now supplies.) rcp_seeded(1.0, 1.0) == 1.0.
+  static __device__ __forceinline__ double rcp_seeded(double s, double y2) {
+    double e = __builtin_fma(-s, y2, 1.0) + 0x1p-54;
+    double r = __builtin_fma(y2, e, y2);
+    e = __builtin_fma(-s, r, 1.0);
+    return __builtin_fma(r, e, r);
+  }
   // RN(1 / b), the CORRECTLY ROUNDED reciprocal: div_r's single residual step returns the correctly rounded quotient
   // only then (Markstein). Two Newton steps from the 2^-24 seed leave RN((1 / b)(1 - eps^2)), eps^2 ~ 2^-96: the
   // neighbour of RN(1 / b) wherever 1 / b lies closer than that to the midpoint of two doubles -- b a few ulp below a
   // power of two (1 / (1 - k 2^-53) is k^2 2^-106 above one), and sporadic others. With that reciprocal, 1 ulp low,
   // 0x1.6666666666663p-1 / 0x1.ffffffffffffbp-1 came out 1 ulp low on the hardware (and k = 11, 13; the compiler's
-  // own expansion returns the same wrong bits; tests/test_hard_rounding_gpu.py). The third step starts within 1 ulp:
-  // its residual e = (B + j) 2^-106 is exact and RN(r + r e) = RN((1 / b)(1 - e^2)) is RN(1 / b) for every b but one
-  // mantissa, all ones, where r + r e is an exact tie between the two fixed points 2^-n and 2^-n (1 + 2^-52) of the
-  // step; RN(1 / b) is the odd one of the two, whichever the iteration sits on: the select sets its last bit.
+  // own expansion returns the same wrong bits; tests/test_hard_rounding_gpu.py). A last Newton step that STARTS
+  // within 1 ulp repairs that: its residual e = 1 - b r is exact and RN(r + r e) = RN((1 / b)(1 - e^2)) is RN(1 / b)
+  // for every b but one mantissa, all ones. There 1 / b = 2^-n (1 + 2^-53 + ...) lies just above the midpoint of the
+  // step's two fixed points, 2^-n (even) and 2^-n (1 + 2^-52) (odd, and RN(1 / b)); from the even one r + r e is an
+  // exact tie and round-to-even stays there, from the odd one the step stays odd.
+  // As written: ONE cubic step, r0 (1 + e + e^2) with e = 1 - b r0, takes the seed's 2^-24 to 2^-72 (it stands for
+  // two of the three plain Newton steps this function took before), and it carries a relative bias of +2^-54; then
+  // the exact last step. The bias does what an integer select on the divisor's mantissa did before (set the last bit
+  // for an all-ones b) without an instruction of its own beyond one add. It must lie strictly between the biased
+  // step's residual noise and half an ulp:
+  //   * above the noise. The roundings of e, of e + 2^-54 and inside the fma are below 2^-76 of r and the truncation
+  //     e^3 is 2^-72, so before its final rounding the biased step stands within 2^-71 of (1 / b)(1 + 2^-54): 1/4 to
+  //     1/2 ulp ABOVE 1 / b (2^-54 relative is that for a reciprocal's mantissa in [1, 2)), whatever the seed's sign.
+  //     For an all-ones b that is 3/4 to 1 ulp above the even fixed point: RN gives the odd one, always. Without a
+  //     bias, or with a negative one, a seed that undershoots arrives on the even point (mantissa 2^53 - 1 wrong).
+  //   * below 1/2 ulp. RN of a point less than 1/2 ulp above 1 / b is within 1 ulp of 1 / b and never more than
+  //     1/4 ulp below it: the last step's premise. With 2^-52 (1 to 2 ulp) the step starts too far out and the
+  //     mantissas 2^53 - 1, - 3 come out wrong, with 2^-51 also 2^53 - 5.
+  //   A quadratic first step (r0 (1 + e)) leaves 2^-48, far above any admissible bias: 2^53 - k wrong for k = 1 .. 15
+  //   and more. 2^-53 .. 2^-58 pass the model as 2^-54 does (tests/test_rcp_bias.py: every mantissa 2^53 - k and
+  //   2^52 + k for odd k < 4096, the constructed division families, seed errors over +-2^-22; on the device
+  //   tests/test_rcp_bias_gpu.py, op 18, and the 2.98e6 quotients of tests/test_hard_rounding_gpu.py).
+  // What the callers rely on is kept: rcp_refined(1.0) == 1.0 exactly (norm_unit<true> and the tails divide by a
+  // selected 1.0) and the reciprocal of every power of two is exact -- v_rcp_f64 returns it or a neighbour, the
+  // biased step stays less than 1/2 ulp away from it and the exact last step returns it. Zero, infinite and NaN
+  // divisors give NaN as the three plain steps did (b = +-0: r = +-inf, e = NaN; b = +-inf: r = +-0, e = -b r + 1 =
+  // NaN; NaN: NaN), which is what v_div_fixup expects: it decides those cases from a and b alone and never reads q.
   static __device__ __forceinline__ double rcp_refined(double b) {
     double r = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    const bool ones = ((unsigned long long)__double_as_longlong(b) | 0xfff0000000000000ull) == ~0ull;
-    return __longlong_as_double(__double_as_longlong(r) | (long long)ones);
+    e = __builtin_fma(e, e, e + 0x1p-54);   // e + e^2 + 2^-54: the cubic step, biased upwards
+    r = __builtin_fma(r, e, r);             // within 1 ulp of 1 / b; an all-ones b: the odd fixed point
+    e = __builtin_fma(-b, r, 1.0);          // exact from within 1 ulp
+    r = __builtin_fma(r, e, r);             // RN(1 / b) (Markstein)
+    return r;
   }
   // a / b given r = rcp_refined(b); v_div_fixup supplies the IEEE results for
   // zero / infinite / NaN operands
@@ -232,19 +259,26 @@ template <> struct Mth<MATH_XACT> {
     return mk(div_r(a.x, s, r), div_r(a.y, s, r), div_r(a.z, s, r));
   }
   static __device__ __forceinline__ double norm(V3 a) { return sqrt(sqn(a)); }
-  // s = |a| and the refined reciprocal of s (shared by the divisions by this norm). It must be rcp_refined(s):
-  // a reciprocal taken from the sqrt iteration (2h + one Newton step) passed 1.2e9 random a / sqrt(b) checks but is
-  // NOT always the same double -- for s = 1 - 2^-53 (the norm of a cross product of two unit vectors!) both 1.0 and
-  // 1 + 2^-52 are fixed points of the Newton step, it lands on the other one than v_rcp_f64 does, and the quotient
-  // of a numerator on a rounding tie came out 1 ulp off (found by tools/fuzz_parity.py, now in the test suite).
-  static __device__ __forceinline__ void norm_rcp(V3 a, double &s, double &rs) { s = sqrt(sqn(a)); rs = rcp_refined(s); }
+  // s = |a| and the refined reciprocal of s (shared by the divisions by this norm). It must be RN(1 / s), the double
+  // rcp_refined(s) returns: a reciprocal taken from the sqrt iteration as 2h + ONE plain Newton step passed 1.2e9
+  // random a / sqrt(b) checks but is NOT always that double -- for s = 1 - 2^-53 (the norm of a cross product of two
+  // unit vectors!) both 1.0 and 1 + 2^-52 are fixed points of the Newton step, it landed on the other one than
+  // v_rcp_f64 does, and the quotient of a numerator on a rounding tie came out 1 ulp off (found by
+  // tools/fuzz_parity.py, now in the test suite). rcp_seeded is that shortcut made right: the same seed, then the
+  // biased step and the exact last step, which give RN(1 / s) from any seed within 2^-40 (tests/test_rcp_bias.py,
+  // ops 19 / 20 in tests/test_rcp_bias_gpu.py). The chain behind s is four FMAs and an add instead of v_rcp_f64,
+  // five FMAs and an add; the root's zero / infinity select stays off it (the chain reads the unselected root: for
+  // z = 0 or inf both give NaN, as rcp_refined(0) and rcp_refined(inf) do).
+  static __device__ __forceinline__ void norm_rcp(V3 a, double &s, double &rs) { norm_rcp_z(sqn(a), s, rs); }
   static __device__ __forceinline__ double rcp_for(double s) { return rcp_refined(s); }
-  // (with sqrt_pos here too the one-slot kernels came out slower on one box -- C2 281.7 vs 279.1 us, C3 1276 vs 1250 us:
-  // instruction scheduling, not arithmetic; measured per site with tools/ab.sh)
-  static __device__ __forceinline__ void norm_rcp_z(double z, double &s, double &rs) { s = sqrt(z); rs = rcp_refined(s); }
+  // (s keeps its zero / infinity select here: returning the select-free root once made the one-slot kernels slower on
+  // one box -- C2 281.7 vs 279.1 us, C3 1276 vs 1250 us: instruction scheduling, not arithmetic; measured per site. Only
+  // the reciprocal's chain reads the select-free root now, so that the select is off the root -> divide chain; with
+  // that, C2 / C3 / C5 x 8 measured + 0.4 / + 0.9 / + 1.3 % over rcp_refined(s), NOTES 1.)
+  static __device__ __forceinline__ void norm_rcp_z(double z, double &s, double &rs) { double y2; const double g = sqrt_seed(z, y2); rs = rcp_seeded(g, y2); s = zinf(z, g); }
   // the same for a caller that discards everything derived from s unless z is positive and finite (the circular term's
   // |rv|: the term only counts for squaredNorm != 0): no zero / infinity select behind the iteration (3 instructions)
-  static __device__ __forceinline__ void norm_rcp_zpos(double z, double &s, double &rs) { s = sqrt_pos(z); rs = rcp_refined(s); }
+  static __device__ __forceinline__ void norm_rcp_zpos(double z, double &s, double &rs) { double y2; s = sqrt_seed(z, y2); rs = rcp_seeded(s, y2); }
   static __device__ __forceinline__ double div_n(double x, double s, double rs) { return div_r(x, s, rs); }
   static __device__ __forceinline__ V3 div3_n(V3 a, double s, double rs) {
     return mk(div_r(a.x, s, rs), div_r(a.y, s, rs), div_r(a.z, s, rs));
@@ -258,15 +292,19 @@ template <> struct Mth<MATH_XACT> {
   template <bool TP = false>
   static __device__ __forceinline__ void norm_unit(V3 a, double &s, V3 &u) {
     double z = sqn(a);
-    s = sqrt(z);
-    const double rs = TP ? 0.0 : rcp_refined(s);
+    double y2;
+    const double g = sqrt_seed(z, y2);
+    s = zinf(z, g);
+    const double rs = TP ? 0.0 : rcp_seeded(g, y2);
     // (fixup-free divisions: the quotient is only used when squaredNorm > 0 -- then s is a positive normal and
     // |a_i| <= s -- or the divisor is the exact 1.0)
     if (TP) {
-      // (round 3: ONE select, on the divisor; its refined reciprocal is computed behind it -- rcp_refined(1.0) is 1.0
-      // exactly: v_rcp_f64 returns 1.0 or a neighbour, and the Newton steps round 1 - delta^2 to 1.0)
-      const double sd = (z > 0.0) ? s : 1.0;
-      u = div3_n_pos(a, sd, rcp_refined(sd));
+      // (round 3: ONE select, on the divisor; its refined reciprocal is computed behind it. The root's seed takes the
+      // same select: rcp_seeded(1.0, 1.0) is 1.0 exactly -- e = 0 + 2^-54, 1 + 2^-54 rounds to 1.0, and the last
+      // step's residual is 0. The tails, which go through rcp_for, rely on rcp_refined(1.0) == 1.0 in the same way.)
+      const bool pos = z > 0.0;
+      const double sd = pos ? g : 1.0;
+      u = div3_n_pos(a, sd, rcp_seeded(sd, pos ? y2 : 1.0));
     } else {
       V3 q = div3_n_pos(a, s, rs);
       u = (z > 0.0) ? q : a;
@@ -277,13 +315,14 @@ template <> struct Mth<MATH_XACT> {
   template <bool TP = false>
   static __device__ __forceinline__ V3 normalized(V3 a) {
     const double z = sqn(a);
-    const double s = sqrt_pos(z);
+    double y2;
+    const double s = sqrt_seed(z, y2);
     if (TP) {
       const bool pos = z > 0.0;
       const double sd = pos ? s : 1.0;
-      return div3_n_pos(a, sd, rcp_refined(sd));
+      return div3_n_pos(a, sd, rcp_seeded(sd, pos ? y2 : 1.0));
     }
-    const V3 q = div3_n_pos(a, s, rcp_refined(s));
+    const V3 q = div3_n_pos(a, s, rcp_seeded(s, y2));
     return (z > 0.0) ? q : a;
   }
 };
@@ -718,8 +757,9 @@ __device__ __forceinline__ V3 current_vector(int type, V3 agent_vel, V3 goal_vec
       // the quotient is NaN in every component, as is the vector normalized() would return (to_obs * NaN is NaN in
       // every component, so cur is)
       const double z = sqn(cur);
-      const double s = M::sqrt_pos(z);
-      const V3 q = M::div3_n_pos(cur, s, M::rcp_refined(s));
+      double y2;
+      const double s = M::sqrt_seed(z, y2);
+      const V3 q = M::div3_n_pos(cur, s, M::rcp_seeded(s, y2));
       return (z < 0x1.79ca10c924223p-67) ? mk(0.0, 0.0, 1.0) : q;
     }
     double s;

@@ -334,8 +334,9 @@ __device__ __forceinline__ V3 cv_close_threshold(const V3 cur, const bool keep, 
   typedef Mth<MATH> M;
   if constexpr (MATH == MATH_XACT) {
     const double z = sqn(cur);
-    const double s = M::sqrt_pos(z);
-    quot = M::div3_n_pos(cur, s, M::rcp_refined(s));
+    double y2;
+    const double s = M::sqrt_seed(z, y2);
+    quot = M::div3_n_pos(cur, s, M::rcp_seeded(s, y2));
     const bool tiny = (z < 0x1.79ca10c924223p-67) && !keep;
     return mk(tiny ? 0.0 : quot.x, tiny ? 0.0 : quot.y, tiny ? 1.0 : quot.z);
   } else {

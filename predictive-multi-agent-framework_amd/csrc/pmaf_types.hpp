@@ -251,7 +251,7 @@ void pmaf_k_launch_restart_paths(const DevView &D, const double *pos, hipStream_
 void pmaf_k_launch_link_force(int n, const double *link_pos, const double *k_r, const double *sent, double rad,
                               double shell, double *out, hipStream_t s);
 void pmaf_k_launch_debug_math(int op, int n, const double *a, const double *b, double *out, hipStream_t s);
-// ops 13..17 of pmaf_debug_math (pmaf_k_dbgmath.hip)
+// ops 13..20 of pmaf_debug_math (pmaf_k_dbgmath.hip)
 void pmaf_k_launch_debug_math_ext(int op, int n, const double *a, const double *b, double *out, hipStream_t s);
 void pmaf_k_launch_winner(const DevView &D, double *dst, hipStream_t s);
 // path part of the winner records whose headers k_manager wrote into dst: the selected agents' paths out of `paths`
