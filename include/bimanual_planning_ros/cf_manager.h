@@ -73,6 +73,17 @@ struct CrossAudit {
   int other_step_at(int agent, int other) const { return other_step.at((size_t)agent * n_other + other); }
 };
 
+// result of CfManager::selectClear: the cheapest agent whose path is clear of the live list (pmaf.h, "selection against
+// the live list")
+struct ClearSelection {
+  int pick = -1;            // the selected agent
+  int rule = -1;            // 0: the previous pick was kept, 1: the cheapest clear agent, 2: no clear agent with a comparable cost
+  int n_clear = 0;          // agents whose audit window is clear of the list
+  double cost = 0.0;        // the pick's cost (evaluateAgents')
+  double clearance = 0.0;   // ... its least clearance inside the window [m]
+  int first_violation = 0;  // ... and its first path point below the margin; the window's size if none
+};
+
 class CfManager {
   pmaf_planner *h_ = nullptr;
   int n_agents_ = 0;
@@ -99,6 +110,7 @@ class CfManager {
   // setThrowOnNumericFault(true) and re-init() after catching; getHealth() reports the same bits without throwing.
   bool throw_on_numeric_fault_ = false;
   bool selected_path_on_ = false;         // enableSelectedPath survives a re-init
+  int prev_pick_ = -1;                    // selectClear's last pick (its hysteresis reference); none after init()
   void touch() { paths_cached_ = false; }
 
   static void check(int rc, const char *what) {
@@ -163,6 +175,7 @@ class CfManager {
       paths_cache_ = std::move(o.paths_cache_);
       paths_cached_ = o.paths_cached_; o.paths_cached_ = false;
       random_vecs_override_ = std::move(o.random_vecs_override_);
+      prev_pick_ = o.prev_pick_;
     }
     return *this;
   }
@@ -206,6 +219,7 @@ class CfManager {
       throw std::invalid_argument("CfManager::init: gain vectors must have equal sizes");  // assert, :50
     remember_best();
     touch();
+    prev_pick_ = -1;
     if (h_) { pmaf_destroy(h_); h_ = nullptr; }
     goal_pos_ = goal_pos;
     k_r_force_ = k_r_force;
@@ -541,6 +555,55 @@ class CfManager {
     if (throw_on_numeric_fault_ && (getHealth() & (PMAF_HEALTH_SETPOINT_NAN | PMAF_HEALTH_FORCE_NAN)))
       throw std::runtime_error("CfManager::planTick: the real agent's set-point / force is not finite (getHealth())");
     return best;
+  }
+  // The cheapest agent whose predicted path keeps `margin` of clearance to the list as it is NOW over its first
+  // `horizon` points (pmaf_select_clear; no reference equivalent: evaluateAgents ignores its list). The manager remembers
+  // its last pick and hands it over as the hysteresis reference (evaluateAgents' 0.9 rule on the clear set); init()
+  // forgets it. adopt: the pick becomes best_agent_ on the device, so that moveRealEEAgent's heuristic follows it
+  // (agent_id selects the gains only). Call after evaluateAgents.
+  ClearSelection selectClear(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                             const bool adopt = true) {
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("selectClear: obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    const int32_t prev = prev_pick_;
+    int32_t pick = -1, rule = -1, n_clear = 0, fv = 0;
+    ClearSelection r;
+    check(pmaf_select_clear(h_, obs.data(), margin, horizon, &prev, adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost,
+                            &r.clearance, &fv),
+          "selectClear");
+    r.pick = pick; r.rule = rule; r.n_clear = n_clear; r.first_violation = fv;
+    prev_pick_ = pick;
+    return r;
+  }
+  // best_agent_ = ee_agents_[agent]->makeCopy() (cf_manager.cpp:346) on the device: the real agent's heuristic and Random
+  // vectors follow `agent` from the next moveRealEEAgent on (pmaf_adopt_best)
+  void adoptBest(const int agent) {
+    require();
+    if (agent < 0 || agent >= n_agents_) throw std::out_of_range("adoptBest: agent index");
+    const int32_t a = agent;
+    check(pmaf_adopt_best(h_, &a), "adoptBest");
+  }
+  // planCallback's sequence with the selection held against the live list: stopPrediction, evaluateAgents,
+  // selectClear(adopt), moveRealEEAgent(agent_id = pick), resetEEAgents to the new set-point, startPrediction. Returns
+  // the pick.
+  int planTickAudited(const std::vector<Obstacle> &obstacles, const double delta_t, const double k_goal_dist,
+                      const double k_path_len, const double k_safe_dist, const double k_workspace,
+                      const Vector6d des_ws_limits, const double margin, const int horizon,
+                      Vector3d *next_position = nullptr, ClearSelection *sel = nullptr) {
+    stopPrediction();
+    evaluateAgents(obstacles, k_goal_dist, k_path_len, k_safe_dist, k_workspace, des_ws_limits);
+    const ClearSelection s = selectClear(obstacles, margin, horizon, true);
+    moveRealEEAgent(obstacles, delta_t, 1, s.pick);
+    double p[3], v[3];
+    check(pmaf_get_real_state(h_, p, v, nullptr), "planTickAudited");
+    resetEEAgents(Vector3d(p[0], p[1], p[2]), Vector3d(v[0], v[1], v[2]), obstacles);
+    startPrediction();
+    if (next_position) *next_position = Vector3d(p[0], p[1], p[2]);
+    if (sel) *sel = s;
+    if (throw_on_numeric_fault_ && (getHealth() & (PMAF_HEALTH_SETPOINT_NAN | PMAF_HEALTH_FORCE_NAN)))
+      throw std::runtime_error("CfManager::planTickAudited: the real agent's set-point / force is not finite (getHealth())");
+    return s.pick;
   }
   // PMAF_HEALTH_* bits of the last planTick / evaluateAgents / moveRealEEAgent (no reference equivalent)
   int getHealth() {

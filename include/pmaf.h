@@ -347,7 +347,9 @@ int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, cons
  * pair [2] = (i, j); *pair_cost = S and *pair_clearance = clearance of the returned pair, both NaN for (-1, -1). The
  * matrix stays on the device between the audit and the reduction; only these results come back. The call selects
  * NOTHING in the handle: the caller applies the pair through what exists -- pmaf_move_real's agent_id (or
- * pmaf_set_best). Intended five-call tick of a bimanual node, both arms in one handle:
+ * pmaf_set_best). pmaf_move_real's agent_id selects the GAINS of the real step only: its heuristic type and Random
+ * vectors are those of the best-agent copy the last pmaf_evaluate made. pmaf_adopt_best (below) makes that copy -- and
+ * with it the heuristic -- follow the pair. Intended five-call tick of a bimanual node, both arms in one handle:
  *   pmaf_stop -> pmaf_evaluate -> pmaf_select_pair -> pmaf_move_real(agent_id = pair) -> pmaf_reset_agents -> pmaf_start
  * Right after pmaf_tick the call is pointless: that call has already moved, reset and restarted, so the paths in the
  * handle belong to the NEW rollout while the costs still describe the old one. Hysteresis over pairs is the caller's
@@ -404,6 +406,54 @@ int pmaf_cross_audit_tracks_slack(pmaf_planner *h, int32_t pop, int32_t n_tracks
 int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, double margin, int32_t late_a,
                            int32_t late_b, int32_t *pair, double *pair_cost, double *pair_clearance, int32_t *feasible,
                            int32_t *pair_steps);
+
+/* ---- selection against the live list; adopting a pick (exports added under ABI 7) ----
+ * pmaf_evaluate restates CfManager::evaluateAgents (B/src/cf_manager.cpp:293-356): its safety term is min_obs_dist,
+ * recorded against the obstacle copies of the previous reset, and it ignores the list it is given. The audits above
+ * say which paths the list as it is NOW blocks, but select nothing. pmaf_select_clear selects: the cheapest agent whose
+ * path is clear of the live list, on the device. No reference equivalent.
+ * The audit window. For population p and agent a with n = n_points[p][a], the window is the first w = min(n, horizon)
+ * points of the CURRENT path. horizon < 1: PMAF_ERR_INVALID; values above max_prediction_steps mean the whole path
+ * (clamped on the host). Inside the window everything is pmaf_evaluate_paths' contract, unchanged: the obstacle track is
+ * iterated, one multiply then one add per component, each rounded; c(k,j) = norm(x_k - o_j^k) - (radius + r_j) in the
+ * build's dot association; every obstacle of obstacles [P][n_obstacles][7] counts, the trailing one included; the
+ * minimum is found with a strict `<` from +infinity; a NaN pair never wins and never violates. Per agent:
+ *   c_a      = min over k < w and j of c(k,j); +infinity for w = 0
+ *   fv_a     = the smallest k < w with c(k,j) < margin for some j, else w
+ *   clear_a  iff fv_a == w
+ * bit for bit what pmaf_evaluate_paths gives on the paths cut to w points.
+ * The rule. cost[a] = what pmaf_get_costs reports at this moment (read from the same device array behind the same
+ * wait, as pmaf_select_pair does).
+ *   m        = the clear agent of minimum cost: strict `<` from +infinity over ascending index (ties go to the
+ *              smallest index; a NaN or +infinite cost never wins)
+ *   rule 0   (keep the previous pick) when m exists, prev_idx is given, q = prev_idx[p] >= 0, clear_q holds and
+ *              cost[m] >= 0.9 * cost[q]: pick = q. evaluateAgents' hysteresis (:344-350) on the clear set, with one
+ *              deliberate difference: a previous pick whose cost is NaN is NOT kept (the reference's !(a < b) keeps it)
+ *   rule 1   (cheapest clear) when m exists and rule 0 does not apply: pick = m
+ *   rule 2   (fallback) when m does not exist -- no clear agent, or none with a comparable cost: the agent that stays
+ *              clear longest: greatest fv_a, then greatest c_a, then smallest index (a strict scan over ascending
+ *              index: the pick is always in [0, N))
+ * pick [P] is required; rule [P], n_clear [P] (number of clear agents), cost [P], clearance [P], first_violation [P]
+ * (cost, c and fv of the pick) may each be NULL. prev_idx [P] or NULL; an entry outside [-1, N) is PMAF_ERR_INVALID;
+ * margin and the list are range-checked like every input.
+ * State. With adopt == 0 the call changes no planner state (the list does NOT become the resident live list either: a
+ * tick sequence with such calls in between is bit-identical to one without). With adopt != 0 every population adopts
+ * its pick exactly as pmaf_adopt_best does. The call waits for the running rollout like the getters do and refuses a
+ * handle whose tick was abandoned (PMAF_ERR_STATE until pmaf_stop). Right after pmaf_tick the call is pointless, for
+ * the reason given at pmaf_select_pair. Intended six-call tick:
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_clear(adopt = 1) -> pmaf_move_real(agent_id = pick) -> pmaf_reset_agents -> pmaf_start */
+int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
+                      int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
+                      int32_t *first_violation);
+/* The device-side best_agent_ = ee_agents_[i]->makeCopy() (B/src/cf_manager.cpp:346) for i = agent_idx[p]; agent_idx
+ * [P], an entry of -1 leaves that population alone, any other entry outside [0, N) is PMAF_ERR_INVALID. The stores are
+ * those of the selection inside pmaf_evaluate when it takes a new agent: has_best = 1, best id = i + 1, best type =
+ * the agent's type, best index = i, and the best agent's Random vectors <- agent i's. Enqueued on the handle's stream;
+ * no host copy of the vectors is made. Afterwards pmaf_get_best and pmaf_evaluate_path speak of the adopted agent, the
+ * next pmaf_move_real steps with its heuristic and vectors, and the next pmaf_evaluate applies its hysteresis to it. The
+ * real agent's own rotation vectors and known flags stay, as they do across a selection. Winner records and the winner
+ * path keep describing pmaf_evaluate's selection. */
+int pmaf_adopt_best(pmaf_planner *h, const int32_t *agent_idx);
 
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last

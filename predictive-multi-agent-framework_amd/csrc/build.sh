@@ -12,6 +12,9 @@
 #                        pmaf_cross_audit.hpp with the cross audit), a unit of its own so that the other units'
 #                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
 #                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
+#   pmaf_k_select.hip    the selection against the live list (pmaf_select_clear / pmaf_adopt_best), a unit of its own for
+#                        the same reason; its object is select.o, outside the k_*.o set like slack.o
+#                        (tests/test_select_clear.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
@@ -95,6 +98,7 @@ kcompile k_mw_m1 pmaf_k_mw.hip -DPMAF_MW_MATH=1
 kcompile k_mw_m3 pmaf_k_mw.hip -DPMAF_MW_MATH=3 -ffp-contract=fast
 kcompile k_misc pmaf_k_misc.hip
 kcompile slack pmaf_k_slack.hip
+kcompile select pmaf_k_select.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
 ( $CXX $HFLAGS -c pmaf_host.cpp -o "$OBJ/host.o" 2> "$OBJ/host.log" ) &
 pids+=($!); names+=("host")
@@ -108,8 +112,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o \
   "$OBJ"/host.o "$OBJ"/shard.o -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

@@ -186,6 +186,14 @@ struct pmaf_planner {
   // step matrix, the pair reduction's partials and result, the caller's tracks and their lengths
   char *d_xaudit = nullptr;
   size_t xaudit_bytes = 0;
+  // pmaf_select_clear / pmaf_adopt_best scratch, allocated by the first call; none of it is planner state. Mapped pinned
+  // host memory of the call's own (NOT h_zc: the list must not become the resident live list): the list [P][7][n_obs] |
+  // the result records [P][PMAF_SELECT_REC] | the previous picks [P] int32. On the device: the staged list, the audit's
+  // per-agent clearance and first violation, pmaf_adopt_best's indices for handles of many populations.
+  double *h_sel = nullptr, *d_sel = nullptr;
+  double *d_sel_obs = nullptr, *d_sel_clr = nullptr;
+  int32_t *d_sel_fv = nullptr, *d_adopt_idx = nullptr;
+  double sel_seq = 0.0;         // sequence number of the last pmaf_select_clear (result record entry 7)
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};
@@ -979,6 +987,7 @@ int pmaf_destroy(pmaf_planner *h) {
   if (h->d_audit) (void)hipFree(h->d_audit);
   if (h->h_audit) (void)hipHostFree(h->h_audit);
   if (h->d_xaudit) (void)hipFree(h->d_xaudit);
+  if (h->h_sel) (void)hipHostFree(h->h_sel);
   for (auto &e : h->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto &e : h->ev_inflight) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   if (h->ev_mgr) (void)hipEventDestroy(h->ev_mgr);
@@ -1456,6 +1465,125 @@ int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearan
         if (!v) fail(PMAF_ERR_STATE, "pmaf_evaluate_path: no agent has been selected yet (call pmaf_evaluate / pmaf_tick first)");
     }
     evaluate_paths(h, obstacles, 0.0, true, clearance, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+
+// ---- selection against the live list (include/pmaf.h, "selection against the live list"): pmaf_select_clear,
+// pmaf_adopt_best; kernels in pmaf_k_select.hip ----
+static void select_scratch(pmaf_planner *h) {
+  if (h->h_sel) return;
+  const DevView &D = h->D;
+  const size_t list = (size_t)D.P * 7 * D.n_obs, PN = (size_t)D.P * D.N;
+  const size_t bytes = sizeof(double) * (list + (size_t)D.P * PMAF_SELECT_REC) + sizeof(int32_t) * (size_t)D.P;
+  h->d_sel_obs = h->dalloc_untracked<double>(list);
+  h->d_sel_clr = h->dalloc_untracked<double>(PN);
+  h->d_sel_fv = h->dalloc_untracked<int32_t>(PN);
+  h->d_adopt_idx = h->dalloc_untracked<int32_t>((size_t)D.P);
+  double *hp = nullptr;
+  HIP_CHECK(hipHostMalloc((void **)&hp, bytes, hipHostMallocMapped));
+  std::memset(hp, 0, bytes);
+  h->h_sel = hp;
+  HIP_CHECK(hipHostGetDevicePointer((void **)&h->d_sel, h->h_sel, 0));
+}
+
+// Spin until k_select_pick has published `seq` for every population; bounded like wait_mailbox, and an expired wait
+// abandons the handle the same way (the kernels still read the scratch and may still adopt).
+static void wait_select(pmaf_planner *h, const double *rec, double seq) {
+  if (h->blocking_wait) HIP_CHECK(hipStreamSynchronize(h->stream));
+  std::chrono::steady_clock::time_point t_start{};
+  bool timing = false;
+  for (int p = 0; p < h->D.P; p++) {
+    const volatile double *s = rec + (size_t)p * PMAF_SELECT_REC + 7;
+    unsigned spins = 0;
+    while (*s != seq) {
+#if defined(__x86_64__) || defined(__i386__)
+      __builtin_ia32_pause();
+#else
+      std::this_thread::yield();
+#endif
+      if ((++spins & 0x3fffu) != 0) continue;
+      const auto now = std::chrono::steady_clock::now();
+      if (!timing) { timing = true; t_start = now; }
+      else if (std::chrono::duration<double>(now - t_start).count() > h->tick_timeout_s) {
+        h->tick_abandoned = true;
+        fail(PMAF_ERR_DEVICE, "pmaf_select_clear: no result from the selection kernel within the time limit (PMAF_TICK_TIMEOUT_S); "
+                              "call pmaf_stop() before the next call");
+      }
+      const hipError_t e = hipStreamQuery(h->stream);
+      if (e == hipErrorNotReady) continue;
+      if (e != hipSuccess) throw HipError{e, "hipStreamQuery (selection wait)", __LINE__};
+      if (*s != seq) fail(PMAF_ERR_DEVICE, "pmaf_select_clear: the selection kernel finished without publishing its result");
+    }
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+}
+
+int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
+                      int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
+                      int32_t *first_violation) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && pick, "pmaf_select_clear: NULL argument");
+    const DevView &D = h->D;
+    REQUIRE(horizon >= 1, "pmaf_select_clear: horizon must be >= 1");
+    if (prev_idx)
+      for (int p = 0; p < D.P; p++) REQUIRE(prev_idx[p] >= -1 && prev_idx[p] < D.N, "pmaf_select_clear: prev_idx out of range");
+    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+    check_range(&margin, 1, "margin");
+    h->use_device();
+    require_drained(h, "pmaf_select_clear");
+    sync(h);   // behind the running rollout, like the getters of its results
+    select_scratch(h);
+    const size_t list = (size_t)D.P * 7 * D.n_obs;
+    double *rec = h->h_sel + list;
+    int32_t *prev_h = reinterpret_cast<int32_t *>(rec + (size_t)D.P * PMAF_SELECT_REC);
+    aos_to_soa(obstacles, h->h_sel, D.P, D.n_obs);
+    if (prev_idx) std::memcpy(prev_h, prev_idx, sizeof(int32_t) * (size_t)D.P);
+    SelectArgs A{};
+    A.obs_src = h->d_sel;
+    A.obs = h->d_sel_obs;
+    A.margin = margin;
+    A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
+    A.adopt = adopt ? 1 : 0;
+    A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->d_sel + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
+    A.clr = h->d_sel_clr;
+    A.fv = h->d_sel_fv;
+    A.result = h->d_sel + list;
+    A.seq = (h->sel_seq += 1.0);
+    pmaf_k_launch_select_clear(D, A, h->stream);
+    HIP_CHECK(hipGetLastError());
+    wait_select(h, rec, A.seq);
+    if (adopt) h->has_best_h = 1;
+    for (int p = 0; p < D.P; p++) {
+      const double *r = rec + (size_t)p * PMAF_SELECT_REC;
+      pick[p] = (int32_t)r[0];
+      if (rule) rule[p] = (int32_t)r[1];
+      if (n_clear) n_clear[p] = (int32_t)r[2];
+      if (first_violation) first_violation[p] = (int32_t)r[3];
+      if (cost) cost[p] = r[4];
+      if (clearance) clearance[p] = r[5];
+    }
+  });
+}
+
+int pmaf_adopt_best(pmaf_planner *h, const int32_t *agent_idx) {
+  return guarded([&] {
+    REQUIRE(h && agent_idx, "pmaf_adopt_best: NULL argument");
+    const DevView &D = h->D;
+    for (int p = 0; p < D.P; p++) REQUIRE(agent_idx[p] >= -1 && agent_idx[p] < D.N, "pmaf_adopt_best: agent_idx out of range");
+    h->use_device();
+    require_drained(h, "pmaf_adopt_best");
+    AdoptArgs A{};
+    if (D.P <= PMAF_ADOPT_INLINE) {   // by value in the kernel arguments: nothing for a later call to overwrite
+      for (int p = 0; p < D.P; p++) A.idx_val[p] = agent_idx[p];
+    } else {
+      select_scratch(h);
+      HIP_CHECK(hipStreamSynchronize(h->stream));   // (an earlier call's kernel may still read d_adopt_idx)
+      h->upload(h->d_adopt_idx, agent_idx, (size_t)D.P);
+      A.idx = h->d_adopt_idx;
+    }
+    pmaf_k_launch_adopt_best(D, A, h->stream);   // enqueued: ordered in front of the next manager launch by the stream
+    HIP_CHECK(hipGetLastError());
+    if (agent_idx[0] >= 0) h->has_best_h = 1;   // (has_best_h speaks for population 0)
   });
 }
 

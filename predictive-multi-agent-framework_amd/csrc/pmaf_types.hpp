@@ -223,6 +223,28 @@ struct PairArgs {
   PairResult *result;
 };
 
+// selection against the live list (pmaf_select_clear / pmaf_adopt_best): pmaf_k_select.hip
+#define PMAF_SELECT_REC 8   // doubles per population in the result record: pick, rule, n_clear, first_violation, cost,
+                            // clearance, (unused), sequence number
+struct SelectArgs {
+  const double *obs_src;    // [P][7][n_obs] SoA: the caller's live list in mapped pinned HOST memory (the call's own
+                            // scratch, not the tick's staging buffer: the list does not become the resident one)
+  double *obs;              // the same on the device (k_select_stage)
+  double margin;
+  int horizon;              // 1 .. cap (clamped on the host): the audit window is the first min(n_points, horizon) points
+  int adopt;                // != 0: the pick becomes the population's best agent (k_manager's `take` stores)
+  const int32_t *prev;      // [P] previous pick (-1: none) in mapped pinned host memory, or NULL
+  double *clr;              // [P][N] device scratch: least clearance inside the window
+  int32_t *fv;              // [P][N] device scratch: first violation inside the window
+  double *result;           // [P][PMAF_SELECT_REC] mapped pinned host memory
+  double seq;               // written to result[p][7] after the record (and the adopt stores) are visible to the host
+};
+#define PMAF_ADOPT_INLINE 16
+struct AdoptArgs {
+  const int32_t *idx;       // [P] on the device, or NULL: idx_val (handles of at most PMAF_ADOPT_INLINE populations)
+  int32_t idx_val[PMAF_ADOPT_INLINE];   // agent index per population, -1: leave the population alone
+};
+
 // ---------------------------------------------------------------------------
 // launch interface: implemented in pmaf_k_w64.hip / pmaf_k_grp.hip / pmaf_k_misc.hip / pmaf_k_slack.hip
 // ---------------------------------------------------------------------------
@@ -271,5 +293,9 @@ void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s);
 void pmaf_k_launch_cross_audit_slack(const CrossAuditSlackArgs &A, hipStream_t s);
 // the two stages of the pair reduction back to back
 void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s);
+// pmaf_k_select.hip: k_select_stage, k_select_audit (grid (N, P)) and k_select_pick (grid P) in stream order
+void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream_t s);
+// k_adopt_best on grid P
+void pmaf_k_launch_adopt_best(const DevView &D, const AdoptArgs &A, hipStream_t s);
 // opt the kernels that take dynamic LDS into more than the 64 KB default
 hipError_t pmaf_k_set_lds_limits(size_t lds_manager, size_t lds_rollout);

@@ -71,6 +71,8 @@ SYMBOLS = {
     "pmaf_cross_audit_slack": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip]),
     "pmaf_cross_audit_tracks_slack": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip]),
     "pmaf_select_pair_slack": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip]),
+    "pmaf_select_clear": (C.c_int, [_V, _dp, C.c_double, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp, _dp, _ip]),
+    "pmaf_adopt_best": (C.c_int, [_V, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -416,6 +418,38 @@ class PmafPlanner:
         self._chk(self.L.pmaf_select_pair_slack(self._h, int(pop_a), int(pop_b), float(separation), float(margin), int(late_a),
                                                 int(late_b), _pi(pair), C.byref(cost), C.byref(clr), C.byref(feas), _pi(st)))
         return dict(self._pair_dict(pair, cost, clr, feas), steps=(int(st[0]), int(st[1])))
+
+    # -- selection against the live list; adopting a pick --
+    def select_clear(self, obstacles, margin, horizon, prev=None, adopt=False):
+        """the cheapest agent whose first `horizon` path points keep `margin` of clearance to the live list
+        (pmaf_select_clear): a dict of pick, rule, n_clear, first_violation (int32 [P]) and cost, clearance [P]; prev =
+        the previous pick(s) or None; adopt=True makes the pick the best agent on the device (adopt_best)"""
+        o = self._obs(obstacles)
+        pv = None if prev is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prev, dtype=np.int32), (self.P,)))
+        out = {k: np.zeros(self.P, dtype=np.int32) for k in ("pick", "rule", "n_clear", "first_violation")}
+        out["cost"], out["clearance"] = np.zeros(self.P), np.zeros(self.P)
+        self._chk(self.L.pmaf_select_clear(self._h, _p(o), float(margin), int(horizon), _pi(pv), 1 if adopt else 0,
+                                           _pi(out["pick"]), _pi(out["rule"]), _pi(out["n_clear"]), _p(out["cost"]),
+                                           _p(out["clearance"]), _pi(out["first_violation"])))
+        return {k: (v[0].item() if self.P == 1 else v) for k, v in out.items()}
+
+    def adopt_best(self, idx):
+        """agent idx[p] becomes population p's best agent on the device, -1 leaves it alone (pmaf_adopt_best)"""
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(idx, dtype=np.int32), (self.P,)))
+        self._chk(self.L.pmaf_adopt_best(self._h, _pi(ids)))
+
+    def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None):
+        """the six-call tick: stop, evaluate, select_clear(adopt), move_real(agent_id = pick), reset_agents to the new
+        set-point, start. Returns select_clear's dict, with `best` = evaluate's own selection"""
+        self.stop()
+        best = self.evaluate(cost_gains, ws)
+        sel = self.select_clear(obstacles, margin, horizon, prev=prev, adopt=True)
+        self.move_real(obstacles, dt, 1, sel["pick"])
+        pos, vel, _ = self.real_state()
+        self.last_next_pos, self.last_next_vel = np.array(pos, copy=True), np.array(vel, copy=True)
+        self.reset_agents(pos, vel, obstacles)
+        self.start()
+        return dict(sel, best=best)
 
     def link_force(self, link_pos, k_r_force, obstacles, pop=0):
         lp, k, o = _d(link_pos), _d(k_r_force), self._obs(obstacles)

@@ -134,7 +134,7 @@ class DualArmCoupling:
         self.obstacles = obs
         return obs
 
-    def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None):
+    def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None, adopt=False):
         """One tick of both arms as populations 0 / 1 of ONE handle, the two winners picked TOGETHER: the node's
         five-call sequence with pmaf_select_pair in it (include/pmaf.h "cross audit") --
         stop -> evaluate -> select_pair -> move_real(agent_id = the pair) -> reset -> start. The pair is the cheapest
@@ -144,7 +144,10 @@ class DualArmCoupling:
         feasible, cost, clearance, positions [2][3] (the new set-points).
         late = (late_a, late_b): the pair must keep the margin although arm 0 may run up to late_a steps behind arm 1's
         clock and arm 1 up to late_b behind arm 0's (pmaf_select_pair_slack, include/pmaf.h "cross audit with timing
-        slack"); the dict then also has steps (step_a, step_b). None: the step-against-step audit, as before."""
+        slack"); the dict then also has steps (step_a, step_b). None: the step-against-step audit, as before.
+        adopt=True: the pair also becomes the two populations' best agents (pmaf_adopt_best) before the real step, so
+        that the step's heuristic type and Random vectors follow the pair; move_real's agent_id selects the gains only.
+        False: the real step keeps the heuristic of evaluate's own selection, as before."""
         assert planner.P == 2, "pair_tick drives the two populations of one handle"
         planner.stop()
         best = planner.evaluate(cost_gains, ws)
@@ -154,6 +157,8 @@ class DualArmCoupling:
             out = planner.select_pair_slack(0, 1, agent_radius + self.radius, margin, late[0], late[1])
         pair = out["pair"] if out["pair"][0] >= 0 else tuple(int(b) for b in best)   # no comparable pair: each arm's own
         obs = self.coupled_obstacles(planner.real_state()[0], advance)
+        if adopt:
+            planner.adopt_best(np.asarray(pair, dtype=np.int32))
         planner.move_real(obs, dt, 1, np.asarray(pair, dtype=np.int32))
         pos, vel, _ = planner.real_state()
         planner.reset_agents(pos, vel, obs)
