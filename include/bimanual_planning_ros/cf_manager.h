@@ -84,6 +84,22 @@ struct ClearSelection {
   int first_violation = 0;  // ... and its first path point below the margin; the window's size if none
 };
 
+// result of CfManager::selectClearAgainst: the cheapest agent whose path is clear of the live list AND keeps apart from
+// one of the other arm's paths (pmaf.h, "joint selection")
+struct JointSelection {
+  int pick = -1;            // the selected agent (-1: nothing comparable), and ...
+  int track = -1;           // ... the path of other_paths it was selected against
+  int rule = -1;            // 0: the previous pick was kept, 1: the cheapest feasible pair, 2: the fallback, -1: none
+  int n_feasible = 0;       // feasible (agent, other path) pairs
+  int n_clear = 0;          // agents whose audit window is clear of the list
+  double cost = 0.0;        // the pick's cost (evaluateAgents')
+  double clearance = 0.0;   // the pair's least distance minus separation [m]
+  double obstacle_clearance = 0.0;  // the pick's least clearance to the list inside the window [m]
+  int first_violation = 0;  // ... and its first path point below the margin; the window's size if none
+  double worst_excess = 0.0;        // min(obstacle_clearance - margin, clearance - pair_margin)
+  int step = -1, other_step = -1;   // the steps at which the pair's least distance is reached
+};
+
 class CfManager {
   pmaf_planner *h_ = nullptr;
   int n_agents_ = 0;
@@ -111,6 +127,7 @@ class CfManager {
   bool throw_on_numeric_fault_ = false;
   bool selected_path_on_ = false;         // enableSelectedPath survives a re-init
   int prev_pick_ = -1;                    // selectClear's last pick (its hysteresis reference); none after init()
+  int prev_track_ = -1;                   // selectClearAgainst's last other path, beside prev_pick_
   void touch() { paths_cached_ = false; }
 
   static void check(int rc, const char *what) {
@@ -176,6 +193,7 @@ class CfManager {
       paths_cached_ = o.paths_cached_; o.paths_cached_ = false;
       random_vecs_override_ = std::move(o.random_vecs_override_);
       prev_pick_ = o.prev_pick_;
+      prev_track_ = o.prev_track_;
     }
     return *this;
   }
@@ -220,6 +238,7 @@ class CfManager {
     remember_best();
     touch();
     prev_pick_ = -1;
+    prev_track_ = -1;
     if (h_) { pmaf_destroy(h_); h_ = nullptr; }
     goal_pos_ = goal_pos;
     k_r_force_ = k_r_force;
@@ -497,15 +516,15 @@ class CfManager {
   }
 
  private:
-  CrossAudit crossAuditImpl(const std::vector<std::vector<Vector3d>> &other_paths, const double separation, const bool slack,
-                            const int late, const int other_late) {
-    require();
-    if (other_paths.empty()) throw std::out_of_range("crossAudit: no paths given");
+  // the other arm's paths as the track calls take them: [n][max_prediction_steps][3] and the point counts
+  void packTracks(const std::vector<std::vector<Vector3d>> &other_paths, std::vector<double> &tracks, std::vector<int32_t> &len,
+                  const char *who) const {
+    if (other_paths.empty()) throw std::out_of_range(std::string(who) + ": no paths given");
     const size_t n = other_paths.size(), row = (size_t)cap_ * 3;
-    std::vector<double> tracks(n * row, 0.0);
-    std::vector<int32_t> len(n);
+    tracks.assign(n * row, 0.0);
+    len.assign(n, 0);
     for (size_t j = 0; j < n; ++j) {
-      if (other_paths[j].size() > (size_t)cap_) throw std::out_of_range("crossAudit: a path is longer than max_prediction_steps");
+      if (other_paths[j].size() > (size_t)cap_) throw std::out_of_range(std::string(who) + ": a path is longer than max_prediction_steps");
       len[j] = (int32_t)other_paths[j].size();
       for (size_t k = 0; k < other_paths[j].size(); ++k) {
         const Vector3d &q = other_paths[j][k];
@@ -513,6 +532,14 @@ class CfManager {
         r[0] = q.x(); r[1] = q.y(); r[2] = q.z();
       }
     }
+  }
+  CrossAudit crossAuditImpl(const std::vector<std::vector<Vector3d>> &other_paths, const double separation, const bool slack,
+                            const int late, const int other_late) {
+    require();
+    std::vector<double> tracks;
+    std::vector<int32_t> len;
+    packTracks(other_paths, tracks, len, "crossAudit");
+    const size_t n = other_paths.size();
     CrossAudit r;
     r.n_agents = n_agents_;
     r.n_other = (int)n;
@@ -576,6 +603,54 @@ class CfManager {
     prev_pick_ = pick;
     return r;
   }
+  // The joint pick of one arm per CfManager: the cheapest agent whose first `horizon` path points keep `margin` to the list
+  // as it is NOW -- its trailing obstacle, the sphere at the other arm's last set-point, left out -- AND `pair_margin` to
+  // one of `other_paths` (the other manager's getSelectedPath(), or several candidates), both on the same step grid
+  // (pmaf_select_clear_tracks with skip_trailing; no reference equivalent). separation = the sum of the two bodies'
+  // radii. The manager hands its last pick over as the hysteresis reference, as selectClear does; adopt: the pick
+  // becomes best_agent_ on the device. Call after evaluateAgents.
+  JointSelection selectClearAgainst(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                    const std::vector<std::vector<Vector3d>> &other_paths, const double separation,
+                                    const double pair_margin, const bool adopt = true) {
+    return selectClearAgainstImpl(obstacles, margin, horizon, other_paths, separation, pair_margin, nullptr, adopt);
+  }
+  // ... with timing slack: this arm may run up to `late` steps behind the other arm's clock, the other arm up to
+  // `other_late` behind this one's. std::out_of_range for a negative slack.
+  JointSelection selectClearAgainst(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                    const std::vector<std::vector<Vector3d>> &other_paths, const double separation,
+                                    const double pair_margin, const int late, const int other_late, const bool adopt = true) {
+    if (late < 0 || other_late < 0) throw std::out_of_range("selectClearAgainst: a slack must be >= 0");
+    const int32_t slack[2] = {late, other_late};
+    return selectClearAgainstImpl(obstacles, margin, horizon, other_paths, separation, pair_margin, slack, adopt);
+  }
+
+ private:
+  JointSelection selectClearAgainstImpl(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                        const std::vector<std::vector<Vector3d>> &other_paths, const double separation,
+                                        const double pair_margin, const int32_t *slack, const bool adopt) {
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("selectClearAgainst: obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    std::vector<double> tracks;
+    std::vector<int32_t> len;
+    packTracks(other_paths, tracks, len, "selectClearAgainst");
+    const int32_t n = (int32_t)other_paths.size();
+    const int32_t prev[2] = {prev_pick_, prev_track_ < n ? prev_track_ : -1};
+    int32_t pair[2] = {-1, -1}, rule = -1, n_feasible = 0, n_clear[2] = {0, 0}, fv[2] = {0, 0}, steps[2] = {-1, -1};
+    double oc[2] = {0.0, 0.0};
+    JointSelection r;
+    check(pmaf_select_clear_tracks(h_, 0, obs.data(), margin, horizon, 1, n, tracks.data(), len.data(), nullptr, separation,
+                                   pair_margin, slack, &prev[0], adopt ? 1 : 0, pair, &rule, &n_feasible, n_clear, &r.cost,
+                                   &r.clearance, oc, fv, &r.worst_excess, steps),
+          "selectClearAgainst");
+    r.pick = pair[0]; r.track = pair[1]; r.rule = rule; r.n_feasible = n_feasible; r.n_clear = n_clear[0];
+    r.obstacle_clearance = oc[0]; r.first_violation = fv[0]; r.step = steps[0]; r.other_step = steps[1];
+    prev_pick_ = pair[0];
+    prev_track_ = pair[1];
+    return r;
+  }
+
+ public:
   // best_agent_ = ee_agents_[agent]->makeCopy() (cf_manager.cpp:346) on the device: the real agent's heuristic and Random
   // vectors follow `agent` from the next moveRealEEAgent on (pmaf_adopt_best)
   void adoptBest(const int agent) {

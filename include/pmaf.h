@@ -455,6 +455,67 @@ int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, i
  * path keep describing pmaf_evaluate's selection. */
 int pmaf_adopt_best(pmaf_planner *h, const int32_t *agent_idx);
 
+/* ---- joint selection: clear of the live list and of each other (exports added under ABI 7) ----
+ * pmaf_select_pair picks a pair that keeps apart but may run through an obstacle that has moved since the reset;
+ * pmaf_select_clear picks each arm alone, so its two picks may collide with each other. These two calls pick the two
+ * arms' agents TOGETHER, on the device: the cheapest pair whose members are both clear of the live list and keep their
+ * distance from each other, with hysteresis and a fallback, and -- when asked -- adopt it. No reference equivalent.
+ * pmaf_select_pair_clear: side A = population pop_a, side B = population pop_b of the handle.
+ * pmaf_select_clear_tracks: side A = population pop, side B = the caller's tracks [n_tracks][cap][3] with
+ * n_track_points [n_tracks], as pmaf_cross_audit_tracks takes them (the other arm's selected path when it lives in
+ * another handle); track_cost [n_tracks] or NULL.
+ * Window. w = min(n_points, horizon) per path, as in pmaf_select_clear; horizon < 1: PMAF_ERR_INVALID; values above
+ * max_prediction_steps are clamped on the host. The same window applies to both sides of the cross audit and to the
+ * tracks (w = min(n_track_points, horizon)).
+ * Obstacle side. Per agent of pop_a and of pop_b, c, fv and clear <=> fv == w are bit for bit pmaf_select_clear's on
+ * obstacles [P][n_obstacles][7] and obstacle_margin. With skip_trailing != 0 the obstacle of index n_obstacles - 1 of
+ * every list is left out of the audit: in the coupled configuration it is the static sphere at the other arm's last
+ * set-point, which the cross audit replaces (the other arm will not stay there). With n_obstacles == 1 that leaves
+ * nothing to audit: c = +infinity and every agent is clear. With skip_trailing == 0 every obstacle counts.
+ * Pair side. clearance(i,j) and its step(s) are bit for bit what pmaf_cross_audit gives on the two path sets cut to
+ * their windows (late == NULL: step against step), or -- late = (late_a, late_b) given -- what pmaf_cross_audit_slack
+ * gives on the cut sets, through its own kernel even for (0, 0). A negative entry is PMAF_ERR_INVALID. All windows share
+ * one horizon, so the hold rule only ever holds a path that really ended inside the window.
+ *   feasible(i,j) iff clear_a[i] and clear_b[j] and clearance(i,j) >= pair_margin   (false for a NaN clearance; tracks:
+ *                 clear_b is true for every track)
+ *   S(i,j)      = cost_a[i] + cost_b[j], one rounded add; the costs are what pmaf_get_costs reports at this moment, as
+ *                 pmaf_select_pair reads them; tracks: cost_b = track_cost, or +0.0 when it is NULL
+ *   m           = the feasible pair of least S: strict `<` from +infinity in row-major order (ties go to the smallest
+ *                 i, then the smallest j; a NaN or +infinite sum never wins)
+ *   rule 1        m exists and rule 0 does not apply: the pair is m
+ *   rule 0 (keep) m exists, prev_pair is given with both entries >= 0, feasible(prev) holds and
+ *                 S(m) >= 0.9 * S(prev) (one rounded multiply): the pair is prev_pair. A NaN S(prev) fails the
+ *                 comparison: the deliberate difference from the reference of pmaf_select_clear
+ *   rule 2 (fallback) no m: with single rounded subtractions ga = c_a[i] - obstacle_margin, gb = c_b[j] -
+ *                 obstacle_margin (absent for tracks), gp = clearance(i,j) - pair_margin and
+ *                 g = ga; if (gb < g) g = gb; if (gp < g) g = gp;  -- the worst excess over its own margin -- the pair
+ *                 of greatest g, strict `>` from -infinity in row-major order. A pair with a NaN gp does not take part
+ *   rule -1       rule 2 found nothing: pair = (-1, -1), costs, clearances and worst_excess NaN, first_violation and
+ *                 steps -1, nothing adopted
+ * prev_pair [2] or NULL; an entry outside [-1, N) -- [-1, n_tracks) for the tracks side -- is PMAF_ERR_INVALID.
+ * Outputs. pair [2] is required, every other pointer may be NULL. *n_feasible = the number of feasible pairs; n_clear
+ * [2] = the numbers of clear agents per side (tracks: n_tracks); *pair_cost = S and *pair_clearance = clearance of the
+ * returned pair; obstacle_clearance [2] and first_violation [2] = c and fv of its two members (tracks: +infinity and
+ * the track's window); *worst_excess = g of the returned pair, computed as above whatever the rule; pair_steps [2] = the
+ * matrix entry's (step, step) or (step_a, step_b).
+ * State. With adopt == 0 the call changes no planner state and the list does not become the resident live list. With
+ * adopt != 0 and a pair other than (-1, -1), pop_a adopts i and pop_b adopts j exactly as pmaf_adopt_best would (tracks:
+ * only pop adopts); other populations are left alone either way. Waiting, the abandoned-tick refusal (PMAF_ERR_STATE
+ * until pmaf_stop) and range checks follow pmaf_select_clear; pop_a == pop_b or an index outside [0, P), n_tracks <= 0
+ * and a track count outside [0, cap] are PMAF_ERR_INVALID as in the cross audit. Intended tick:
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_pair_clear(adopt = 1) -> pmaf_move_real(agent_id = pair) -> pmaf_reset_agents -> pmaf_start */
+int pmaf_select_pair_clear(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double obstacle_margin,
+                           int32_t horizon, int32_t skip_trailing, double separation, double pair_margin, const int32_t *late,
+                           const int32_t *prev_pair, int32_t adopt, int32_t *pair, int32_t *rule, int32_t *n_feasible,
+                           int32_t *n_clear, double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                           int32_t *first_violation, double *worst_excess, int32_t *pair_steps);
+int pmaf_select_clear_tracks(pmaf_planner *h, int32_t pop, const double *obstacles, double obstacle_margin, int32_t horizon,
+                             int32_t skip_trailing, int32_t n_tracks, const double *tracks, const int32_t *n_track_points,
+                             const double *track_cost, double separation, double pair_margin, const int32_t *late,
+                             const int32_t *prev_pair, int32_t adopt, int32_t *pair, int32_t *rule, int32_t *n_feasible,
+                             int32_t *n_clear, double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                             int32_t *first_violation, double *worst_excess, int32_t *pair_steps);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

@@ -194,6 +194,7 @@ struct pmaf_planner {
   double *d_sel_obs = nullptr, *d_sel_clr = nullptr;
   int32_t *d_sel_fv = nullptr, *d_adopt_idx = nullptr;
   double sel_seq = 0.0;         // sequence number of the last pmaf_select_clear (result record entry 7)
+  double pairclear_seq = 0.0;   // ... of the last joint selection (its record's last entry)
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};
@@ -1470,11 +1471,17 @@ int pmaf_evaluate_path(pmaf_planner *h, const double *obstacles, double *clearan
 
 // ---- selection against the live list (include/pmaf.h, "selection against the live list"): pmaf_select_clear,
 // pmaf_adopt_best; kernels in pmaf_k_select.hip ----
+// offset (in doubles) of the joint selection's result record in the select scratch's pinned area
+static size_t select_pairclear_rec(const DevView &D) {
+  return (size_t)D.P * 7 * D.n_obs + (size_t)D.P * PMAF_SELECT_REC + ((size_t)D.P + 1) / 2;
+}
+
 static void select_scratch(pmaf_planner *h) {
   if (h->h_sel) return;
   const DevView &D = h->D;
   const size_t list = (size_t)D.P * 7 * D.n_obs, PN = (size_t)D.P * D.N;
-  const size_t bytes = sizeof(double) * (list + (size_t)D.P * PMAF_SELECT_REC) + sizeof(int32_t) * (size_t)D.P;
+  // list | result records [P] | previous picks [P] (int32, padded to a double) | the joint selection's record
+  const size_t bytes = sizeof(double) * (select_pairclear_rec(D) + PMAF_PAIRCLEAR_REC);
   h->d_sel_obs = h->dalloc_untracked<double>(list);
   h->d_sel_clr = h->dalloc_untracked<double>(PN);
   h->d_sel_fv = h->dalloc_untracked<int32_t>(PN);
@@ -1486,14 +1493,15 @@ static void select_scratch(pmaf_planner *h) {
   HIP_CHECK(hipHostGetDevicePointer((void **)&h->d_sel, h->h_sel, 0));
 }
 
-// Spin until k_select_pick has published `seq` for every population; bounded like wait_mailbox, and an expired wait
+// Spin until a selection kernel has published `seq` in the last entry of each of `count` records of `rec_doubles`
+// doubles (k_select_pick: one per population; k_pairclear_final: one); bounded like wait_mailbox, and an expired wait
 // abandons the handle the same way (the kernels still read the scratch and may still adopt).
-static void wait_select(pmaf_planner *h, const double *rec, double seq) {
+static void wait_select(pmaf_planner *h, const double *rec, int count, size_t rec_doubles, double seq, const char *who) {
   if (h->blocking_wait) HIP_CHECK(hipStreamSynchronize(h->stream));
   std::chrono::steady_clock::time_point t_start{};
   bool timing = false;
-  for (int p = 0; p < h->D.P; p++) {
-    const volatile double *s = rec + (size_t)p * PMAF_SELECT_REC + 7;
+  for (int p = 0; p < count; p++) {
+    const volatile double *s = rec + (size_t)p * rec_doubles + (rec_doubles - 1);
     unsigned spins = 0;
     while (*s != seq) {
 #if defined(__x86_64__) || defined(__i386__)
@@ -1506,13 +1514,13 @@ static void wait_select(pmaf_planner *h, const double *rec, double seq) {
       if (!timing) { timing = true; t_start = now; }
       else if (std::chrono::duration<double>(now - t_start).count() > h->tick_timeout_s) {
         h->tick_abandoned = true;
-        fail(PMAF_ERR_DEVICE, "pmaf_select_clear: no result from the selection kernel within the time limit (PMAF_TICK_TIMEOUT_S); "
-                              "call pmaf_stop() before the next call");
+        fail(PMAF_ERR_DEVICE, std::string(who) + ": no result from the selection kernel within the time limit (PMAF_TICK_TIMEOUT_S); "
+                                                 "call pmaf_stop() before the next call");
       }
       const hipError_t e = hipStreamQuery(h->stream);
       if (e == hipErrorNotReady) continue;
       if (e != hipSuccess) throw HipError{e, "hipStreamQuery (selection wait)", __LINE__};
-      if (*s != seq) fail(PMAF_ERR_DEVICE, "pmaf_select_clear: the selection kernel finished without publishing its result");
+      if (*s != seq) fail(PMAF_ERR_DEVICE, std::string(who) + ": the selection kernel finished without publishing its result");
     }
   }
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
@@ -1543,6 +1551,7 @@ int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, i
     A.obs = h->d_sel_obs;
     A.margin = margin;
     A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
+    A.n_audit = D.n_obs;                             // every obstacle counts, the trailing one included
     A.adopt = adopt ? 1 : 0;
     A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->d_sel + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
     A.clr = h->d_sel_clr;
@@ -1551,7 +1560,7 @@ int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, i
     A.seq = (h->sel_seq += 1.0);
     pmaf_k_launch_select_clear(D, A, h->stream);
     HIP_CHECK(hipGetLastError());
-    wait_select(h, rec, A.seq);
+    wait_select(h, rec, D.P, PMAF_SELECT_REC, A.seq, "pmaf_select_clear");
     if (adopt) h->has_best_h = 1;
     for (int p = 0; p < D.P; p++) {
       const double *r = rec + (size_t)p * PMAF_SELECT_REC;
@@ -1596,8 +1605,9 @@ struct XAuditSlack {
   int32_t late_a, late_b;
 };
 // Device scratch of one call: clearance [n_a][n_b] | partials | result | tracks [n_tracks][cap][3] | step [n_a][n_b] |
-// track lengths [n_tracks] | the slacked calls' second step matrix [n_a][n_b] (doubles first, the int32 parts padded:
-// every part stays 8-byte aligned)
+// track lengths [n_tracks] | the slacked calls' second step matrix [n_a][n_b] | the joint selection's parts: partials |
+// track costs [n_tracks] | windowed lengths [n_a], [n_b] (doubles first, the int32 parts padded: every part stays 8-byte
+// aligned)
 struct XAuditBuf {
   double *clearance;
   PairBest *partial;
@@ -1605,14 +1615,26 @@ struct XAuditBuf {
   double *tracks;
   int32_t *step, *track_len;
   int32_t *step_b;   // (the slacked calls only)
+  // (the joint selection only)
+  PairClearBest *pc_partial;
+  double *track_cost;
+  int32_t *win_a, *win_b;
 };
-static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps) {
+// the joint selection's audit window: the cross audit then runs on the lengths min(n, horizon) (k_pairclear_window), its
+// matrix stays in the scratch, and nothing is copied out
+struct XAuditWindow {
+  int32_t horizon;   // 1 .. cap
+};
+static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps, bool joint = false) {
   const size_t pairs = n_a * n_b;
   if (pairs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "cross audit: the number of pairs must stay below 2^31");
   const size_t b_clr = sizeof(double) * pairs, b_part = sizeof(PairBest) * PMAF_XAUDIT_PARTIALS, b_res = sizeof(PairResult);
   const size_t b_trk = sizeof(double) * n_tracks * (size_t)h->D.cap * 3, b_step = (sizeof(int32_t) * pairs + 7) & ~(size_t)7;
   const size_t b_len = (sizeof(int32_t) * n_tracks + 7) & ~(size_t)7;
-  const size_t total = b_clr + b_part + b_res + b_trk + b_step + b_len + (two_steps ? b_step : 0);
+  const size_t b_pc = sizeof(PairClearBest) * PMAF_XAUDIT_PARTIALS, b_tc = sizeof(double) * n_tracks;
+  const size_t b_wa = (sizeof(int32_t) * n_a + 7) & ~(size_t)7, b_wb = (sizeof(int32_t) * n_b + 7) & ~(size_t)7;
+  const size_t total = b_clr + b_part + b_res + b_trk + b_step + b_len + (two_steps ? b_step : 0) +
+                       (joint ? b_pc + b_tc + b_wa + b_wb : 0);
   if (total > h->xaudit_bytes) {
     if (h->d_xaudit) { (void)hipFree(h->d_xaudit); h->d_xaudit = nullptr; }
     h->xaudit_bytes = 0;
@@ -1628,6 +1650,11 @@ static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t 
   B.step = reinterpret_cast<int32_t *>(p); p += b_step;
   B.track_len = reinterpret_cast<int32_t *>(p); p += b_len;
   B.step_b = two_steps ? reinterpret_cast<int32_t *>(p) : nullptr;
+  if (two_steps) p += b_step;
+  B.pc_partial = joint ? reinterpret_cast<PairClearBest *>(p) : nullptr; p += joint ? b_pc : 0;
+  B.track_cost = joint ? reinterpret_cast<double *>(p) : nullptr; p += joint ? b_tc : 0;
+  B.win_a = joint ? reinterpret_cast<int32_t *>(p) : nullptr; p += joint ? b_wa : 0;
+  B.win_b = joint ? reinterpret_cast<int32_t *>(p) : nullptr;
   return B;
 }
 
@@ -1644,7 +1671,21 @@ static void clamp_slack(const pmaf_planner *h, XAuditSlack *slack, const char *w
 // the launch: set A against set B into the scratch, the step matrices where they are wanted
 static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *paths_a, const int32_t *len_a, int32_t n_a,
                           const double *paths_b, const int32_t *len_b, int32_t n_b, double separation,
-                          const XAuditSlack *slack, bool want_a, bool want_b) {
+                          const XAuditSlack *slack, bool want_a, bool want_b, const XAuditWindow *win = nullptr) {
+  if (win) {   // both sides cut to their windows: the audit kernels read these lengths instead
+    PairWindowArgs W{};
+    W.n_a = len_a;
+    W.n_b = len_b;
+    W.count_a = n_a;
+    W.count_b = n_b;
+    W.cap = h->D.cap;
+    W.horizon = win->horizon;
+    W.len_a = B.win_a;
+    W.len_b = B.win_b;
+    pmaf_k_launch_pairclear_window(W, h->stream);
+    len_a = B.win_a;
+    len_b = B.win_b;
+  }
   CrossAuditSlackArgs S{};
   CrossAuditArgs &A = S.X;
   A.paths_a = paths_a;
@@ -1678,25 +1719,28 @@ static void xaudit_download(pmaf_planner *h, const XAuditBuf &B, size_t pairs, d
 
 // population pop_a's paths against population pop_b's where they lie; the matrix stays in the scratch
 static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, XAuditSlack *slack,
-                                         bool want_a, bool want_b, const char *who) {
+                                         bool want_a, bool want_b, const char *who, const XAuditWindow *win = nullptr) {
   const DevView &D = h->D;
   if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
     fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
   check_range(&separation, 1, "separation");
   clamp_slack(h, slack, who);
   h->use_device();
-  sync(h);   // behind the running rollout, like the getters of its results
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr);
+  if (!win) sync(h);   // behind the running rollout, like the getters of its results (the joint selection has waited)
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr, win != nullptr);
   xaudit_launch(h, B, D.paths + (size_t)pop_a * D.N * D.cap * 3, D.n_points + (size_t)pop_a * D.N, D.N,
                 D.paths + (size_t)pop_b * D.N * D.cap * 3, D.n_points + (size_t)pop_b * D.N, D.N, separation, slack, want_a,
-                want_b);
+                want_b, win);
   return B;
 }
 
-// population pop's paths against the caller's tracks, uploaded into the scratch; the results back to the host
-static void cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
-                               const int32_t *n_track_points, double separation, XAuditSlack *slack, double *clearance,
-                               int32_t *step_a, int32_t *step_b, const char *who) {
+// population pop's paths against the caller's tracks, uploaded into the scratch; the results back to the host (the
+// joint selection: no clearance pointer, the matrix stays in the scratch; step_a / step_b then only say which step
+// matrices to keep, and track_cost [n_tracks] or NULL is uploaded beside the tracks)
+static XAuditBuf cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
+                                    const int32_t *n_track_points, double separation, XAuditSlack *slack, double *clearance,
+                                    int32_t *step_a, int32_t *step_b, const char *who, const XAuditWindow *win = nullptr,
+                                    const double *track_cost = nullptr) {
   const DevView &D = h->D;
   REQUIRE(pop >= 0 && pop < D.P, std::string(who) + ": population out of range");
   REQUIRE(n_tracks > 0, std::string(who) + ": n_tracks must be > 0");
@@ -1711,13 +1755,15 @@ static void cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, c
     std::memcpy(packed.data() + t * row, tracks + t * row, sizeof(double) * 3 * (size_t)n_track_points[t]);
   }
   h->use_device();
-  sync(h);
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks, slack != nullptr);
+  if (!win) sync(h);
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)n_tracks, (size_t)n_tracks, slack != nullptr, win != nullptr);
   HIP_CHECK(hipMemcpyAsync(B.track_len, n_track_points, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
+  if (track_cost) HIP_CHECK(hipMemcpyAsync(B.track_cost, track_cost, sizeof(double) * (size_t)n_tracks, hipMemcpyHostToDevice, h->stream));
   h->upload(B.tracks, packed.data(), packed.size());
   xaudit_launch(h, B, D.paths + (size_t)pop * D.N * D.cap * 3, D.n_points + (size_t)pop * D.N, D.N, B.tracks, B.track_len,
-                n_tracks, separation, slack, step_a != nullptr, step_b != nullptr);
-  xaudit_download(h, B, (size_t)D.N * n_tracks, clearance, step_a, step_b);
+                n_tracks, separation, slack, step_a != nullptr, step_b != nullptr, win);
+  if (clearance) xaudit_download(h, B, (size_t)D.N * n_tracks, clearance, step_a, step_b);
+  return B;
 }
 
 // the pair pick over the matrix cross_audit_populations left in the scratch. The costs are read where pmaf_get_costs
@@ -1810,6 +1856,149 @@ int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double
         h->download(pair_steps + 1, B.step_b + o, 1);
       }
     }
+  });
+}
+
+// ---- joint selection (include/pmaf.h, "joint selection: clear of the live list and of each other"):
+// pmaf_select_pair_clear, pmaf_select_clear_tracks. One path for both: the select path's audit (k_select_stage,
+// k_select_audit into its scratch), the cross audit path above with a window, then pmaf_k_pairclear.hip's reduction over
+// what both left on the device. Side B is population pop_b, or -- pop_b < 0 -- the caller's tracks. ----
+struct PairClearSideB {
+  int32_t pop_b, n_tracks;
+  const double *tracks;
+  const int32_t *n_track_points;
+  const double *track_cost;
+};
+struct PairClearOut {
+  int32_t *pair, *rule, *n_feasible, *n_clear;
+  double *pair_cost, *pair_clearance, *obstacle_clearance;
+  int32_t *first_violation;
+  double *worst_excess;
+  int32_t *pair_steps;
+};
+static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSideB &sb, const double *obstacles,
+                              double obstacle_margin, int32_t horizon, int32_t skip_trailing, double separation,
+                              double pair_margin, const int32_t *late, const int32_t *prev_pair, int32_t adopt,
+                              const PairClearOut &out, const std::string &who) {
+  const DevView &D = h->D;
+  const bool tracks = sb.pop_b < 0;
+  REQUIRE(horizon >= 1, who + ": horizon must be >= 1");
+  REQUIRE(pop_a >= 0 && pop_a < D.P, who + ": population out of range");
+  if (!tracks && (sb.pop_b >= D.P || sb.pop_b == pop_a)) fail(PMAF_ERR_INVALID, who + ": need two different populations of the handle");
+  if (tracks) REQUIRE(sb.n_tracks > 0, who + ": n_tracks must be > 0");
+  const int32_t n_b = tracks ? sb.n_tracks : D.N;
+  if (prev_pair)
+    REQUIRE(prev_pair[0] >= -1 && prev_pair[0] < D.N && prev_pair[1] >= -1 && prev_pair[1] < n_b, who + ": prev_pair out of range");
+  XAuditSlack slack{0, 0};
+  if (late) slack = XAuditSlack{late[0], late[1]};
+  clamp_slack(h, late ? &slack : nullptr, who.c_str());
+  check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+  check_range(&obstacle_margin, 1, "obstacle_margin");
+  check_range(&pair_margin, 1, "pair_margin");
+  check_range(&separation, 1, "separation");
+  if (tracks && sb.track_cost) check_range(sb.track_cost, (size_t)sb.n_tracks, "track_cost");
+  h->use_device();
+  require_drained(h, who.c_str());
+  sync(h);   // behind the running rollout, like the getters of its results
+  select_scratch(h);
+  // 1. the obstacle side of every population, as pmaf_select_clear runs it
+  aos_to_soa(obstacles, h->h_sel, D.P, D.n_obs);
+  XAuditWindow win{horizon < D.cap ? horizon : D.cap};   // (above the cap: the whole path)
+  SelectArgs S{};
+  S.obs_src = h->d_sel;
+  S.obs = h->d_sel_obs;
+  S.margin = obstacle_margin;
+  S.horizon = win.horizon;
+  S.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;
+  S.clr = h->d_sel_clr;
+  S.fv = h->d_sel_fv;
+  pmaf_k_launch_select_audit(D, S, h->stream);
+  HIP_CHECK(hipGetLastError());
+  // 2., 3. the windowed lengths and the cross audit on them; the matrix stays in the scratch
+  const bool want = out.pair_steps != nullptr;
+  int32_t keep = 0;   // (cross_audit_tracks takes "this step matrix is wanted" as a pointer)
+  const XAuditBuf B = tracks ? cross_audit_tracks(h, pop_a, sb.n_tracks, sb.tracks, sb.n_track_points, separation,
+                                                  late ? &slack : nullptr, nullptr, want ? &keep : nullptr,
+                                                  want ? &keep : nullptr, who.c_str(), &win, sb.track_cost)
+                             : cross_audit_populations(h, pop_a, sb.pop_b, separation, late ? &slack : nullptr, want, want,
+                                                       who.c_str(), &win);
+  // 4., 5. the joint reduction, the rule, the record and the adopt stores
+  const size_t rec_at = select_pairclear_rec(D);
+  double *rec = h->h_sel + rec_at;
+  PairClearArgs A{};
+  A.clearance = B.clearance;
+  A.step_a = want ? B.step : nullptr;
+  A.step_b = want && late ? B.step_b : nullptr;
+  A.cost_a = D.costs + (size_t)pop_a * D.N;
+  A.clr_a = h->d_sel_clr + (size_t)pop_a * D.N;
+  A.fv_a = h->d_sel_fv + (size_t)pop_a * D.N;
+  if (tracks) {
+    A.cost_b = sb.track_cost ? B.track_cost : nullptr;
+  } else {
+    A.cost_b = D.costs + (size_t)sb.pop_b * D.N;
+    A.clr_b = h->d_sel_clr + (size_t)sb.pop_b * D.N;
+    A.fv_b = h->d_sel_fv + (size_t)sb.pop_b * D.N;
+  }
+  A.len_a = B.win_a;
+  A.len_b = B.win_b;
+  A.n_a = D.N;
+  A.n_b = n_b;
+  A.pop_a = pop_a;
+  A.pop_b = tracks ? -1 : sb.pop_b;
+  A.obstacle_margin = obstacle_margin;
+  A.pair_margin = pair_margin;
+  A.prev_i = prev_pair ? prev_pair[0] : -1;
+  A.prev_j = prev_pair ? prev_pair[1] : -1;
+  A.adopt = adopt ? 1 : 0;
+  A.partial = B.pc_partial;
+  A.result = h->d_sel + rec_at;
+  A.seq = (h->pairclear_seq += 1.0);
+  pmaf_k_launch_pairclear(D, A, h->stream);
+  HIP_CHECK(hipGetLastError());
+  wait_select(h, rec, 1, PMAF_PAIRCLEAR_REC, A.seq, who.c_str());
+  out.pair[0] = (int32_t)rec[0];
+  out.pair[1] = (int32_t)rec[1];
+  if (adopt && out.pair[0] >= 0 && (pop_a == 0 || sb.pop_b == 0)) h->has_best_h = 1;   // (has_best_h speaks for population 0)
+  if (out.rule) *out.rule = (int32_t)rec[2];
+  if (out.n_feasible) *out.n_feasible = (int32_t)rec[3];
+  if (out.n_clear) { out.n_clear[0] = (int32_t)rec[4]; out.n_clear[1] = (int32_t)rec[5]; }
+  if (out.pair_cost) *out.pair_cost = rec[6];
+  if (out.pair_clearance) *out.pair_clearance = rec[7];
+  if (out.obstacle_clearance) { out.obstacle_clearance[0] = rec[8]; out.obstacle_clearance[1] = rec[9]; }
+  if (out.first_violation) { out.first_violation[0] = (int32_t)rec[10]; out.first_violation[1] = (int32_t)rec[11]; }
+  if (out.worst_excess) *out.worst_excess = rec[12];
+  if (out.pair_steps) { out.pair_steps[0] = (int32_t)rec[13]; out.pair_steps[1] = (int32_t)rec[14]; }
+}
+
+int pmaf_select_pair_clear(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double obstacle_margin,
+                           int32_t horizon, int32_t skip_trailing, double separation, double pair_margin, const int32_t *late,
+                           const int32_t *prev_pair, int32_t adopt, int32_t *pair, int32_t *rule, int32_t *n_feasible,
+                           int32_t *n_clear, double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                           int32_t *first_violation, double *worst_excess, int32_t *pair_steps) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && pair, "pmaf_select_pair_clear: NULL argument");
+    REQUIRE(pop_b >= 0, "pmaf_select_pair_clear: need two different populations of the handle");
+    select_pair_clear(h, pop_a, PairClearSideB{pop_b, 0, nullptr, nullptr, nullptr}, obstacles, obstacle_margin, horizon,
+                      skip_trailing, separation, pair_margin, late, prev_pair, adopt,
+                      PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
+                                   first_violation, worst_excess, pair_steps},
+                      "pmaf_select_pair_clear");
+  });
+}
+
+int pmaf_select_clear_tracks(pmaf_planner *h, int32_t pop, const double *obstacles, double obstacle_margin, int32_t horizon,
+                             int32_t skip_trailing, int32_t n_tracks, const double *tracks, const int32_t *n_track_points,
+                             const double *track_cost, double separation, double pair_margin, const int32_t *late,
+                             const int32_t *prev_pair, int32_t adopt, int32_t *pair, int32_t *rule, int32_t *n_feasible,
+                             int32_t *n_clear, double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                             int32_t *first_violation, double *worst_excess, int32_t *pair_steps) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && tracks && n_track_points && pair, "pmaf_select_clear_tracks: NULL argument");
+    select_pair_clear(h, pop, PairClearSideB{-1, n_tracks, tracks, n_track_points, track_cost}, obstacles, obstacle_margin,
+                      horizon, skip_trailing, separation, pair_margin, late, prev_pair, adopt,
+                      PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
+                                   first_violation, worst_excess, pair_steps},
+                      "pmaf_select_clear_tracks");
   });
 }
 

@@ -30,12 +30,15 @@
 //                  the ascending strict scan finds. Then the rule, the result record into mapped pinned host memory
 //                  behind a sequence number (as k_manager's mailbox), and -- when asked -- the adopt stores.
 // k_adopt_best     the adopt stores alone, one wave per population: k_manager's `take` block
-//                  (best_agent_ = ee_agents_[i]->makeCopy(), B/src/cf_manager.cpp:346).
+//                  (best_agent_ = ee_agents_[i]->makeCopy(), B/src/cf_manager.cpp:346; adopt_agent, pmaf_adopt.hpp).
+// The joint selection (pmaf_k_pairclear.hip) launches k_select_stage and k_select_audit as they are and hands the audit
+// SelectArgs::n_audit = n_obs - 1 when it leaves the trailing obstacle to the cross audit; pmaf_select_clear passes n_obs.
 // Three launches in stream order; no last-block-done counter.
 #include <hip/hip_runtime.h>
 
 #include "pmaf_types.hpp"
 #include "pmaf_device.hpp"
+#include "pmaf_adopt.hpp"
 
 using namespace pmaf;
 
@@ -51,7 +54,9 @@ __global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_select_audit(DevView
   __shared__ int s_v[PMAF_SELECT_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pop = blockIdx.y, a = blockIdx.x;
-  const int n_obs = D.n_obs;
+  const int n_obs = D.n_obs;       // the lists' stride
+  const int n_audit = A.n_audit;   // the audited obstacles: n_obs, or n_obs - 1 (the joint selection skips the trailing one)
+  PMAF_BOUND(n_audit >= 0 && n_audit <= n_obs);
   const size_t pa = (size_t)pop * D.N + a;
   int n = D.n_points[pa];
   PMAF_BOUND(n >= 0 && n <= D.cap);
@@ -70,9 +75,9 @@ __global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_select_audit(DevView
   double best = inf;
   int viol = 0x7fffffff;
   if (k0 < k1) {
-    for (int j0 = 0; j0 < n_obs; j0 += 64) {   // one pass over the quarter per obstacle tile
+    for (int j0 = 0; j0 < n_audit; j0 += 64) {   // one pass over the quarter per obstacle tile
       const int j = j0 + lane;
-      const bool jv = j < n_obs;
+      const bool jv = j < n_audit;
       const int jc = jv ? j : 0;
       V3 q = mk(o[jc], o[n_obs + jc], o[2 * (size_t)n_obs + jc]);
       // predictObstacles' v * dt, rounded once: the same double in every step of the chain
@@ -115,20 +120,6 @@ __global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_select_audit(DevView
     }
     A.clr[pa] = best;
     A.fv[pa] = (viol == 0x7fffffff) ? w : viol;
-  }
-}
-
-// k_manager's `take` block for agent i of population pop
-__device__ __forceinline__ void adopt_agent(const DevView &D, int pop, int i, int lane) {
-  const int n_obs = D.n_obs;
-  const double *src = D.rnd + ((size_t)pop * D.N + i) * 3 * n_obs;
-  double *dst = D.best_rnd + (size_t)pop * 3 * n_obs;
-  for (int e = lane; e < 3 * n_obs; e += 64) dst[e] = src[e];
-  if (lane == 0) {
-    D.has_best[pop] = 1;
-    D.best_id[pop] = i + 1;
-    D.best_type[pop] = D.types[i];
-    D.best_idx[pop] = i;
   }
 }
 
@@ -211,10 +202,14 @@ __global__ __launch_bounds__(64) void k_adopt_best(DevView D, AdoptArgs A) {
   adopt_agent(D, pop, i, threadIdx.x);
 }
 
-void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream_t s) {
+void pmaf_k_launch_select_audit(const DevView &D, const SelectArgs &A, hipStream_t s) {
   const int total = D.P * 7 * D.n_obs;
   hipLaunchKernelGGL(k_select_stage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, A.obs_src, A.obs);
   hipLaunchKernelGGL(k_select_audit, dim3((unsigned)D.N, (unsigned)D.P), dim3(64 * PMAF_SELECT_WAVES), 0, s, D, A);
+}
+
+void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream_t s) {
+  pmaf_k_launch_select_audit(D, A, s);
   hipLaunchKernelGGL(k_select_pick, dim3((unsigned)D.P), dim3(64), 0, s, D, A);
 }
 

@@ -232,6 +232,8 @@ struct SelectArgs {
   double *obs;              // the same on the device (k_select_stage)
   double margin;
   int horizon;              // 1 .. cap (clamped on the host): the audit window is the first min(n_points, horizon) points
+  int n_audit;              // obstacles 0 .. n_audit - 1 of every list are audited (the lists' stride stays n_obs): n_obs, or
+                            // n_obs - 1 when the joint selection leaves the trailing obstacle to the cross audit
   int adopt;                // != 0: the pick becomes the population's best agent (k_manager's `take` stores)
   const int32_t *prev;      // [P] previous pick (-1: none) in mapped pinned host memory, or NULL
   double *clr;              // [P][N] device scratch: least clearance inside the window
@@ -243,6 +245,38 @@ struct SelectArgs {
 struct AdoptArgs {
   const int32_t *idx;       // [P] on the device, or NULL: idx_val (handles of at most PMAF_ADOPT_INLINE populations)
   int32_t idx_val[PMAF_ADOPT_INLINE];   // agent index per population, -1: leave the population alone
+};
+
+// joint selection (pmaf_select_pair_clear / pmaf_select_clear_tracks): pmaf_k_pairclear.hip
+#define PMAF_PAIRCLEAR_REC 16   // doubles of the result record: i, j, rule, n_feasible, n_clear[2], pair cost, pair clearance,
+                                // obstacle clearance[2], first violation[2], worst excess, steps[2], sequence number
+// the windowed lengths min(n_points, horizon) of both sides, which the cross audit kernels then read as their lengths
+struct PairWindowArgs {
+  const int32_t *n_a, *n_b;          // [count_a], [count_b] points per path
+  int count_a, count_b, cap, horizon;
+  int32_t *len_a, *len_b;            // [count_a], [count_b] device scratch
+};
+// running results of the joint reduction: the cheapest feasible sum, the greatest worst excess (carried NEGATED: both
+// are minima under (value, index); 0x7fffffff: nothing won) and the number of feasible pairs
+struct PairClearBest {
+  double s, ng;
+  int32_t si, gi, nfeas, pad;
+};
+struct PairClearArgs {
+  const double *clearance;           // [n_a][n_b] on the device (the cross audit's output on the windowed lengths)
+  const int32_t *step_a, *step_b;    // [n_a][n_b] or NULL; step_b NULL: the step-against-step audit, (step_a, step_a)
+  const double *cost_a, *cost_b;     // [n_a], [n_b]; cost_b NULL: +0.0 (tracks without costs)
+  const double *clr_a, *clr_b;       // [n_a], [n_b] k_select_audit's least clearance; clr_b / fv_b NULL: side B is tracks
+  const int32_t *fv_a, *fv_b;        // [n_a], [n_b] k_select_audit's first violation
+  const int32_t *len_a, *len_b;      // [n_a], [n_b] the windows (PairWindowArgs)
+  int n_a, n_b;
+  int pop_a, pop_b;                  // the populations that adopt; pop_b < 0: tracks
+  double obstacle_margin, pair_margin;
+  int prev_i, prev_j;                // the previous pair, -1: none
+  int adopt;
+  PairClearBest *partial;            // [PMAF_XAUDIT_PARTIALS] first-stage results
+  double *result;                    // [PMAF_PAIRCLEAR_REC] mapped pinned host memory
+  double seq;                        // written to result[15] after the record (and the adopt stores) are visible to the host
 };
 
 // ---------------------------------------------------------------------------
@@ -295,6 +329,11 @@ void pmaf_k_launch_cross_audit_slack(const CrossAuditSlackArgs &A, hipStream_t s
 void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s);
 // pmaf_k_select.hip: k_select_stage, k_select_audit (grid (N, P)) and k_select_pick (grid P) in stream order
 void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream_t s);
+// the first two of them alone: the per-agent clearance and first violation into A.clr / A.fv, no pick
+void pmaf_k_launch_select_audit(const DevView &D, const SelectArgs &A, hipStream_t s);
+// pmaf_k_pairclear.hip: k_pairclear_window; k_pairclear_reduce and k_pairclear_final back to back
+void pmaf_k_launch_pairclear_window(const PairWindowArgs &A, hipStream_t s);
+void pmaf_k_launch_pairclear(const DevView &D, const PairClearArgs &A, hipStream_t s);
 // k_adopt_best on grid P
 void pmaf_k_launch_adopt_best(const DevView &D, const AdoptArgs &A, hipStream_t s);
 // opt the kernels that take dynamic LDS into more than the 64 KB default

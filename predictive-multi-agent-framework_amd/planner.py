@@ -73,6 +73,11 @@ SYMBOLS = {
     "pmaf_select_pair_slack": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip]),
     "pmaf_select_clear": (C.c_int, [_V, _dp, C.c_double, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp, _dp, _ip]),
     "pmaf_adopt_best": (C.c_int, [_V, _ip]),
+    "pmaf_select_pair_clear": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                         _ip, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _ip]),
+    "pmaf_select_clear_tracks": (C.c_int, [_V, C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _dp,
+                                           C.c_double, C.c_double, _ip, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip,
+                                           _dp, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -437,6 +442,56 @@ class PmafPlanner:
         """agent idx[p] becomes population p's best agent on the device, -1 leaves it alone (pmaf_adopt_best)"""
         ids = np.ascontiguousarray(np.broadcast_to(np.asarray(idx, dtype=np.int32), (self.P,)))
         self._chk(self.L.pmaf_adopt_best(self._h, _pi(ids)))
+
+    # -- joint selection: both arms' agents together, clear of the live list and of each other --
+    @staticmethod
+    def _joint_outputs():
+        i1, i2, d1, d2 = (lambda: np.zeros(1, dtype=np.int32)), (lambda: np.zeros(2, dtype=np.int32)), (lambda: np.zeros(1)), (lambda: np.zeros(2))
+        o = {"pair": i2(), "rule": i1(), "n_feasible": i1(), "n_clear": i2(), "cost": d1(), "clearance": d1(),
+             "obstacle_clearance": d2(), "first_violation": i2(), "worst_excess": d1(), "steps": i2()}
+        args = [(_pi if v.dtype == np.int32 else _p)(v) for v in o.values()]
+        return o, args
+
+    @staticmethod
+    def _joint_dict(o):
+        out = {}
+        for k, v in o.items():
+            if v.size == 2:
+                out[k] = (v[0].item(), v[1].item())
+            else:
+                out[k] = v[0].item()
+        return out
+
+    @staticmethod
+    def _pair_arg(v):
+        return None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(2))
+
+    def select_pair_clear(self, pop_a, pop_b, obstacles, obstacle_margin, horizon, separation, pair_margin,
+                          skip_trailing=False, late=None, prev_pair=None, adopt=False):
+        """the cheapest pair (i of pop_a, j of pop_b) whose members' first `horizon` path points keep obstacle_margin to
+        the live list and pair_margin to each other (pmaf_select_pair_clear): a dict of pair (i, j), rule, n_feasible,
+        n_clear (2), cost, clearance, obstacle_clearance (2), first_violation (2), worst_excess, steps (2).
+        skip_trailing: leave the lists' last obstacle to the cross audit; late = (late_a, late_b) or None; prev_pair =
+        the previous pair or None; adopt=True makes the pair the two populations' best agents on the device"""
+        o, args = self._joint_outputs()
+        lt, pv = self._pair_arg(late), self._pair_arg(prev_pair)
+        self._chk(self.L.pmaf_select_pair_clear(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)), float(obstacle_margin),
+                                                int(horizon), 1 if skip_trailing else 0, float(separation), float(pair_margin),
+                                                _pi(lt), _pi(pv), 1 if adopt else 0, *args))
+        return self._joint_dict(o)
+
+    def select_clear_tracks(self, pop, obstacles, obstacle_margin, horizon, tracks, n_track_points, separation, pair_margin,
+                            track_cost=None, skip_trailing=False, late=None, prev_pair=None, adopt=False):
+        """select_pair_clear with side B from the caller: tracks [n_tracks][cap][3] of n_track_points points each and
+        track_cost [n_tracks] or None (pmaf_select_clear_tracks); the same dict, pair = (agent of pop, track)"""
+        tr, n = self._tracks(tracks, n_track_points)
+        tc = None if track_cost is None else _d(track_cost).reshape(n.size)
+        o, args = self._joint_outputs()
+        lt, pv = self._pair_arg(late), self._pair_arg(prev_pair)
+        self._chk(self.L.pmaf_select_clear_tracks(self._h, int(pop), _p(self._obs(obstacles)), float(obstacle_margin), int(horizon),
+                                                  1 if skip_trailing else 0, n.size, _p(tr), _pi(n), _p(tc), float(separation),
+                                                  float(pair_margin), _pi(lt), _pi(pv), 1 if adopt else 0, *args))
+        return self._joint_dict(o)
 
     def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None):
         """the six-call tick: stop, evaluate, select_clear(adopt), move_real(agent_id = pick), reset_agents to the new

@@ -121,6 +121,7 @@ class DualArmCoupling:
         # obstacles: [2][n_obs][7], row -1 of each arm is replaced every tick
         self.obstacles = np.array(obstacles, dtype=np.float64, copy=True)
         self.radius = self_collision_radius
+        self.prev_pair = None   # the last pair of pair_tick(clear=...): its hysteresis reference
 
     def coupled_obstacles(self, ee_positions, advance=None):
         """ee_positions [2][3] = both arms' current real-agent positions"""
@@ -134,7 +135,8 @@ class DualArmCoupling:
         self.obstacles = obs
         return obs
 
-    def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None, adopt=False):
+    def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None, adopt=False,
+                  clear=None):
         """One tick of both arms as populations 0 / 1 of ONE handle, the two winners picked TOGETHER: the node's
         five-call sequence with pmaf_select_pair in it (include/pmaf.h "cross audit") --
         stop -> evaluate -> select_pair -> move_real(agent_id = the pair) -> reset -> start. The pair is the cheapest
@@ -147,10 +149,29 @@ class DualArmCoupling:
         slack"); the dict then also has steps (step_a, step_b). None: the step-against-step audit, as before.
         adopt=True: the pair also becomes the two populations' best agents (pmaf_adopt_best) before the real step, so
         that the step's heuristic type and Random vectors follow the pair; move_real's agent_id selects the gains only.
-        False: the real step keeps the heuristic of evaluate's own selection, as before."""
+        False: the real step keeps the heuristic of evaluate's own selection, as before.
+        clear = dict(margin=..., horizon=...): the pair must also be clear of the list this tick will use, over the first
+        `horizon` points of both paths (pmaf_select_pair_clear, include/pmaf.h "joint selection"): each arm's trailing
+        sphere at the other arm's last set-point is left to the cross audit (skip_trailing), the previous tick's pair is
+        the hysteresis reference, and adopt is carried out by the same call. The dict is select_pair_clear's plus
+        feasible (rule 0 or 1) and positions. None: as before."""
         assert planner.P == 2, "pair_tick drives the two populations of one handle"
         planner.stop()
         best = planner.evaluate(cost_gains, ws)
+        if clear is not None:
+            obs = self.coupled_obstacles(planner.real_state()[0], advance)
+            out = planner.select_pair_clear(0, 1, obs, clear["margin"], clear["horizon"], agent_radius + self.radius, margin,
+                                            skip_trailing=True, late=late, prev_pair=self.prev_pair, adopt=adopt)
+            pair = out["pair"] if out["pair"][0] >= 0 else tuple(int(b) for b in best)   # no comparable pair: each arm's own
+            self.prev_pair = out["pair"]
+            planner.move_real(obs, dt, 1, np.asarray(pair, dtype=np.int32))
+            pos, vel, _ = planner.real_state()
+            planner.reset_agents(pos, vel, obs)
+            planner.start()
+            out["feasible"] = out["rule"] in (0, 1)
+            out["pair"] = tuple(int(v) for v in pair)
+            out["positions"] = np.array(pos, copy=True)
+            return out
         if late is None:
             out = planner.select_pair(0, 1, agent_radius + self.radius, margin)
         else:
