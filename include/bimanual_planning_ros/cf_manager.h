@@ -709,6 +709,21 @@ class CfManager {
     return out;
   }
 
+  // One arm per CfManager: the rollouts started from now on see the trailing repulsive obstacle -- the other arm -- on
+  // `track` instead of resting at its last set-point: point min(k, size - 1) at prediction step k (pmaf_set_repulsive_track,
+  // include/pmaf.h "repulsive track"; no reference equivalent). Typically the other manager's getSelectedPath(), or the
+  // path out of its winner record, from the point that belongs to this tick on. An empty track detaches. The live list
+  // keeps its sphere for the real step. std::runtime_error where the handle's rollout kernel cannot follow a track (more
+  // than 60 field obstacles, another arithmetic policy).
+  void setRepulsiveTrack(const std::vector<Vector3d> &track) {
+    require();
+    std::vector<double> pts;
+    pts.reserve(track.size() * 3);
+    for (const Vector3d &q : track) { pts.push_back(q.x()); pts.push_back(q.y()); pts.push_back(q.z()); }
+    const int32_t len = (int32_t)track.size();
+    check(pmaf_set_repulsive_track(h_, track.empty() ? nullptr : pts.data(), &len, len > 0 ? len : 1), "setRepulsiveTrack");
+  }
+
   // ---- synchronous stepping API (no callers in the reference; B/src/cf_manager.cpp:220-224, 238-244, 265-291) ----
   // Deviation: after any of these calls startPrediction() needs a resetEEAgents() / setInitialPosition() first
   // (std::runtime_error otherwise): rollouts start from the population's reset state, the reference's threads would

@@ -516,6 +516,44 @@ int pmaf_select_clear_tracks(pmaf_planner *h, int32_t pop, const double *obstacl
                              int32_t *n_clear, double *pair_cost, double *pair_clearance, double *obstacle_clearance,
                              int32_t *first_violation, double *worst_excess, int32_t *pair_steps);
 
+/* ---- repulsive track: rollouts that follow the other arm's predicted path (exports added under ABI 7) ----
+ * A rollout sees the trailing repulsive obstacle on the straight line o_M + k v_M dt. The audits above can report that
+ * the other arm will not be there; nothing above lets a rollout plan around where it WILL be. A population p may
+ * therefore have a track y_0 ... y_{L-1}, L >= 1. While it has one, every rollout of p changes repelForce
+ * (B/src/cf_agent.cpp:159-181) in one way: at step k (k = 0 is the step from the start state) the obstacle's position
+ * is y_{min(k, L-1)} -- the cross audit's hold rule -- instead of the iterated o_M + k v_M dt. Nothing else changes:
+ * the radius is the list's radius; the field obstacles advance by predictObstacles; the trailing obstacle's velocity
+ * is not used (repelForce reads none); scoring, the real step and pmaf_move_real see the live list as ever; known[M]
+ * is carried through. L == 0: no track, the population behaves exactly as without these calls. A track equal to the
+ * iterated straight line gives bit-identical rollouts. Points of index >= max_prediction_steps are never read. No
+ * reference equivalent. Tracks are inputs, not planner state: pmaf_save_state blobs do not hold them.
+ * Known limit: coupled arms each follow the other's PREVIOUS selection, so two arms can alternate between two
+ * answers; pmaf_select_pair_clear's hysteresis (rule 0) is the damper.
+ * Route. The variant that follows a track exists for the one-slot wave-per-agent kernel of the default arithmetic
+ * policy (<= 60 field obstacles, both ordered sums, PLAIN and general step; not the priority-slicing loop of handles
+ * with more waves than SIMDs). On any other route a track is never silently ignored: pmaf_set_repulsive_track /
+ * pmaf_couple_tracks return PMAF_ERR_STATE with a message naming the route, and so do pmaf_start / pmaf_tick when the
+ * route became unsupported after the attach.
+ * pmaf_set_repulsive_track: track [P][max_len][3], len [P]; takes effect from the next pmaf_start / pmaf_tick.
+ *   track == NULL, len == NULL or every len == 0 detaches. A point inside len that is NaN or outside the supported
+ *   numeric range, len < 0 or len > max_len: PMAF_ERR_INVALID. Waits for a running rollout as the setters do; the upload
+ *   runs in stream order on the handle's stream into a grow-only device buffer.
+ * pmaf_couple_tracks: src_pop [P], -1: none. In front of every rollout launch of this handle, population p with
+ *   src_pop[p] = q >= 0 gets as its track the selected path of q -- the path of agent best_idx[q] as it lies in the path
+ *   buffer after the tick's selection and before the rollout overwrites it -- from point `shift` >= 0 on:
+ *   L = max(n_points - shift, 1) (a path of no more than shift points: its last point alone), the last point held. While
+ *   q has no selection yet (no pmaf_evaluate / pmaf_tick so far) L = 0. q == p or q >= P: PMAF_ERR_INVALID. NULL
+ *   uncouples. A coupling and an uploaded track on the same population: the coupling wins while it is set. In the
+ *   five-call tick pmaf_reset_agents cuts every path to its first point before pmaf_start launches the rollout: on a
+ *   coupled handle it takes the selected paths first (after pmaf_adopt_best, if the caller adopts), and the rollout
+ *   pmaf_start launches follows those; pmaf_set_initial_position discards what was taken. Coupled
+ *   handles launch one small copy kernel between the manager kernel and the rollout; others keep the two-launch tick.
+ * pmaf_get_repulsive_track: the tracks the last launched rollout used (waits for it): len [P], and -- track != NULL --
+ *   track [P][max_len][3]; PMAF_ERR_INVALID when max_len is shorter than one of them. */
+int pmaf_set_repulsive_track(pmaf_planner *h, const double *track, const int32_t *len, int32_t max_len);
+int pmaf_couple_tracks(pmaf_planner *h, const int32_t *src_pop, int32_t shift);
+int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32_t max_len);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

@@ -18,6 +18,10 @@
 #   pmaf_k_pairclear.hip the joint selection (pmaf_select_pair_clear / pmaf_select_clear_tracks): the windowed lengths, the
 #                        joint reduction and its final block; a unit of its own for the same reason, object pairclear.o
 #                        (tests/test_pair_clear.py holds its kernels to no scratch through the resource record)
+#   pmaf_k_track.hip     the repulsive track (include/pmaf.h): k_rollout_w64_track -- the one-slot wave-per-agent body of
+#                        pmaf_k_w64.hip instantiated with the tracked obstacle, compiled with the one-slot unit's flags --
+#                        and k_track_from_best; a unit of its own for the same reason, object track.o
+#                        (tests/test_sentinel_track.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
@@ -60,6 +64,7 @@ KFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-m
 HFLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -D__HIP_PLATFORM_AMD__ -I$ROCM/include ${PMAF_EXTRA_FLAGS} ${PMAF_EXTRA_HFLAGS}"
 
 DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
+DEPS_TRACK="pmaf_k_w64.hip pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
 FLAGS_CHANGED=0
@@ -71,7 +76,9 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   local o="$OBJ/$stem.o"
   local stale=0
   [ -f "$o" ] || stale=1
-  for d in $src $DEPS_K build.sh; do [ "$d" -nt "$o" ] && stale=1; done
+  local extra=""
+  [ "$src" = pmaf_k_track.hip ] && extra=$DEPS_TRACK
+  for d in $src $DEPS_K $extra build.sh; do [ "$d" -nt "$o" ] && stale=1; done
   [ "$FLAGS_CHANGED" = 1 ] && stale=1
   [ "$stale" = 0 ] && return 0
   ( $HIPCC $KFLAGS "$@" -c "$src" -o "$o" 2> "$OBJ/$stem.log" ) &
@@ -104,6 +111,8 @@ kcompile slack pmaf_k_slack.hip
 kcompile select pmaf_k_select.hip
 kcompile pairclear pmaf_k_pairclear.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
+# (the flags of k_w64_m2_t1: the same body)
+kcompile track pmaf_k_track.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
 ( $CXX $HFLAGS -c pmaf_host.cpp -o "$OBJ/host.o" 2> "$OBJ/host.log" ) &
 pids+=($!); names+=("host")
 ( $CXX $HFLAGS -c pmaf_shard.cpp -o "$OBJ/shard.o" 2> "$OBJ/shard.log" ) &
@@ -116,8 +125,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o \
   "$OBJ"/host.o "$OBJ"/shard.o -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

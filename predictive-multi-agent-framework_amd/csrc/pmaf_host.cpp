@@ -19,6 +19,7 @@
 #include "pmaf_types.hpp"
 #include "pmaf_lpa_model.hpp"
 #include "pmaf_route.hpp"
+#include "pmaf_track.hpp"
 
 using namespace pmaf;
 
@@ -195,6 +196,26 @@ struct pmaf_planner {
   int32_t *d_sel_fv = nullptr, *d_adopt_idx = nullptr;
   double sel_seq = 0.0;         // sequence number of the last pmaf_select_clear (result record entry 7)
   double pairclear_seq = 0.0;   // ... of the last joint selection (its record's last entry)
+  // ---- repulsive track (include/pmaf.h "repulsive track"): inputs, not planner state -- none of it is in the checkpoint blob.
+  // The device buffer [P][stride][3] + lengths [P] (grow-only) holds what the next rollout launch follows: the caller's
+  // upload, overwritten for coupled populations by k_track_from_best in front of every launch. The host keeps the upload
+  // ([P][up_max][3], up_len) so that uncoupling or a grown buffer can put it back.
+  struct Track {
+    double *d_pts = nullptr;
+    int32_t *d_len = nullptr, *d_src = nullptr;   // d_src: [P] source population of the coupling (-1: none)
+    int stride = 0;                               // points per population the device buffer holds
+    std::vector<double> up;
+    std::vector<int32_t> up_len;
+    int up_max = 0;
+    bool uploaded = false;                        // some up_len > 0
+    bool coupled = false;
+    // the coupled tracks were taken in front of a reset that rewrites the paths (pmaf_reset_agents of the five-call tick):
+    // the next rollout launch follows them instead of copying again
+    bool captured = false;
+    std::vector<int32_t> src;
+    int shift = 0;
+    bool on() const { return uploaded || coupled; }
+  } trk;
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};
@@ -348,6 +369,10 @@ static bool dispatch_rollout(pmaf_planner *h, hipEvent_t e0, hipEvent_t e1) {
       reroute(h);
       return dispatch_rollout(h, e0, e1);
     case pmaf_route::WAVE_PER_AGENT:
+      if (h->trk.on()) {   // (launch_rollout has checked Route::carries_track)
+        const TrackArgs T{h->trk.d_pts, h->trk.d_len, h->trk.stride};
+        return pmaf_k_launch_w64_track(h->D, h->cp, T, r.dpp_sum, r.plain, r.lds_rollout, h->stream, e0, e1);
+      }
       return pmaf_k_launch_w64(h->D, h->cp, r.tiles, r.math, r.dpp_sum, r.plain, r.lds_rollout, h->stream, e0, e1, r.sliced);
     case pmaf_route::GROUP:
       return pmaf_k_launch_grp(h->D, h->cp, r.lpa, r.tiles, r.math, r.n_blocks, r.lds_rollout, h->stream, e0, e1);
@@ -357,7 +382,60 @@ static bool dispatch_rollout(pmaf_planner *h, hipEvent_t e0, hipEvent_t e1) {
   return pmaf_k_launch_generic(h->D, h->cp, r.lpa, r.n_blocks, r.lds_rollout, h->stream, e0, e1);
 }
 
+// A track is never silently ignored: the launch the route names must have the variant that follows it.
+static void require_track_route(const pmaf_planner *h, const pmaf_route::Route &r, const char *who) {
+  if (r.carries_track) return;
+  fail(PMAF_ERR_STATE, std::string(who) + ": the repulsive track needs the one-slot wave-per-agent kernel of the default arithmetic "
+       "policy (<= 60 field obstacles, one wave per SIMD at most); this handle's route is the " + pmaf_route::family_name(r.family) +
+       " kernel" + (r.family == pmaf_route::WAVE_PER_AGENT ? (r.sliced ? " with the priority-slicing loop" : r.slots > 1 ?
+       " with several obstacle slots per lane" : " of another arithmetic policy") : ""));
+}
+
+// (Re)build the device buffer from the host's copy of the upload: stride = the longest of the upload's max_len and --
+// coupled -- the path capacity. Stream order; the caller has drained the stream where a rollout may still read it.
+static void upload_tracks(pmaf_planner *h) {
+  pmaf_planner::Track &t = h->trk;
+  const int P = h->D.P;
+  int need = std::max(1, t.uploaded ? t.up_max : 0);
+  if (t.coupled) need = std::max(need, h->D.cap);
+  if (!t.d_len) {
+    HIP_CHECK(hipMalloc((void **)&t.d_len, sizeof(int32_t) * P));
+    HIP_CHECK(hipMalloc((void **)&t.d_src, sizeof(int32_t) * P));
+  }
+  if (need > t.stride) {
+    if (t.d_pts) HIP_CHECK(hipFree(t.d_pts));
+    t.d_pts = nullptr;
+    HIP_CHECK(hipMalloc((void **)&t.d_pts, sizeof(double) * (size_t)P * need * 3));
+    t.stride = need;
+  }
+  std::vector<double> pts((size_t)P * t.stride * 3, 0.0);
+  std::vector<int32_t> len(P, 0), src(P, -1);
+  for (int p = 0; p < P; p++) {
+    if (t.uploaded) {
+      len[p] = t.up_len[p];
+      std::memcpy(pts.data() + (size_t)p * t.stride * 3, t.up.data() + (size_t)p * t.up_max * 3, sizeof(double) * 3 * (size_t)len[p]);
+    }
+    if (t.coupled && t.src[p] >= 0) { src[p] = t.src[p]; len[p] = 0; }   // (until k_track_from_best has run)
+  }
+  h->upload(t.d_pts, pts.data(), pts.size());
+  h->upload(t.d_len, len.data(), len.size());
+  h->upload(t.d_src, src.data(), src.size());
+}
+
+// the coupled populations' tracks <- the selected paths as they lie in the scored buffer right now (stream order)
+static void capture_coupled_tracks(pmaf_planner *h) {
+  const CoupleArgs A{h->trk.d_src, h->D.paths, h->trk.d_pts, h->trk.d_len, h->trk.stride, h->trk.shift};
+  pmaf_k_launch_track_from_best(h->D, A, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
+
 static void launch_rollout(pmaf_planner *h) {
+  if (h->trk.on()) {
+    require_track_route(h, h->route, "rollout launch");   // (pmaf_start / pmaf_tick have checked already)
+    // before this rollout overwrites the paths -- unless a reset in front of it already has, and took them first
+    if (h->trk.coupled && !h->trk.captured) capture_coupled_tracks(h);
+    h->trk.captured = false;
+  }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->profiling && (h->prof_phase++ % h->prof_every) == 0) {
     drain_events(h, false);
@@ -988,6 +1066,9 @@ int pmaf_destroy(pmaf_planner *h) {
   if (h->d_audit) (void)hipFree(h->d_audit);
   if (h->h_audit) (void)hipHostFree(h->h_audit);
   if (h->d_xaudit) (void)hipFree(h->d_xaudit);
+  if (h->trk.d_pts) (void)hipFree(h->trk.d_pts);
+  if (h->trk.d_len) (void)hipFree(h->trk.d_len);
+  if (h->trk.d_src) (void)hipFree(h->trk.d_src);
   if (h->h_sel) (void)hipHostFree(h->h_sel);
   for (auto &e : h->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto &e : h->ev_inflight) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1012,6 +1093,7 @@ int pmaf_set_initial_position(pmaf_planner *h, const double *pos) {
     h->upload(D.start_pos, pos, P * 3);
     // CfAgent::setPosition = clear + push_back for every predicted agent
     h->paths_gen++;
+    h->trk.captured = false;   // (the paths start over: nothing taken from the old ones is followed)
     pmaf_k_launch_restart_paths(D, D.start_pos, h->stream);
     HIP_CHECK(hipGetLastError());
     h->real_pos_h.assign(pos, pos + P * 3);
@@ -1052,6 +1134,7 @@ int pmaf_start(pmaf_planner *h) {
     // a finished rollout that was not reset has nothing left to predict
     // (guard B/src/cf_agent.cpp:310-311 is already false)
     if (!h->rollout_pending) return;
+    if (h->trk.on()) require_track_route(h, h->route, "pmaf_start");
     if (!h->cp_valid) {  // no evaluate yet: score with neutral workspace terms, rescored on evaluate
       h->cp = CostParams{};
       h->cp.ws[0] = h->cp.ws[2] = h->cp.ws[4] = INFINITY;
@@ -1061,6 +1144,107 @@ int pmaf_start(pmaf_planner *h) {
     launch_rollout(h);
     h->cp_valid = had_cp;
     if (!had_cp) h->scores_valid = false;
+  });
+}
+
+static void require_drained(pmaf_planner *h, const char *who);
+
+// ---- repulsive track ----
+// attach / detach: the route's `tracked` input follows, and an attach the routed launch cannot carry is refused here
+static void set_tracked(pmaf_planner *h, bool want, const char *who) {
+  if (want) {
+    pmaf_route::Input in = h->route_in;
+    in.tracked = true;
+    require_track_route(h, pmaf_route::route(in), who);
+  }
+  h->route_in.tracked = want;
+  reroute(h);
+}
+
+int pmaf_set_repulsive_track(pmaf_planner *h, const double *track, const int32_t *len, int32_t max_len) {
+  return guarded([&] {
+    REQUIRE(h, "pmaf_set_repulsive_track: NULL handle");
+    h->use_device();
+    require_drained(h, "pmaf_set_repulsive_track");
+    pmaf_planner::Track &t = h->trk;
+    const int P = h->D.P;
+    bool any = false;
+    if (track && len) {
+      REQUIRE(max_len >= 1, "pmaf_set_repulsive_track: max_len must be >= 1");
+      for (int p = 0; p < P; p++) {
+        REQUIRE(len[p] >= 0 && len[p] <= max_len, "pmaf_set_repulsive_track: need 0 <= len <= max_len");
+        check_range(track + (size_t)p * max_len * 3, (size_t)len[p] * 3, "pmaf_set_repulsive_track: track");
+        any = any || len[p] > 0;
+      }
+    }
+    if (any) set_tracked(h, true, "pmaf_set_repulsive_track");
+    sync(h);   // a running rollout still reads the buffer
+    t.uploaded = any;
+    if (any) {
+      // (points past the path capacity are never read: the rollout has at most cap - 1 steps)
+      t.up_max = std::min((int)max_len, h->D.cap);
+      t.up_len.assign(P, 0);
+      t.up.assign((size_t)P * t.up_max * 3, 0.0);
+      for (int p = 0; p < P; p++) {
+        t.up_len[p] = std::min((int)len[p], t.up_max);
+        std::memcpy(t.up.data() + (size_t)p * t.up_max * 3, track + (size_t)p * max_len * 3, sizeof(double) * 3 * (size_t)t.up_len[p]);
+      }
+    } else {
+      t.up.clear(); t.up_len.clear(); t.up_max = 0;
+    }
+    if (t.on()) upload_tracks(h);
+    else set_tracked(h, false, "pmaf_set_repulsive_track");
+  });
+}
+
+int pmaf_couple_tracks(pmaf_planner *h, const int32_t *src_pop, int32_t shift) {
+  return guarded([&] {
+    REQUIRE(h, "pmaf_couple_tracks: NULL handle");
+    h->use_device();
+    require_drained(h, "pmaf_couple_tracks");
+    pmaf_planner::Track &t = h->trk;
+    const int P = h->D.P;
+    bool any = false;
+    if (src_pop) {
+      REQUIRE(shift >= 0, "pmaf_couple_tracks: shift must be >= 0");
+      for (int p = 0; p < P; p++) {
+        REQUIRE(src_pop[p] < P && src_pop[p] != p, "pmaf_couple_tracks: src_pop must be another population of this handle (or -1)");
+        any = any || src_pop[p] >= 0;
+      }
+    }
+    if (any) set_tracked(h, true, "pmaf_couple_tracks");
+    sync(h);
+    t.coupled = any;
+    t.captured = false;
+    if (any) {
+      t.src.assign(P, -1);
+      for (int p = 0; p < P; p++) t.src[p] = src_pop[p] >= 0 ? src_pop[p] : -1;
+      t.shift = shift;
+    } else {
+      t.src.clear(); t.shift = 0;
+    }
+    if (t.on()) upload_tracks(h);
+    else set_tracked(h, false, "pmaf_couple_tracks");
+  });
+}
+
+int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32_t max_len) {
+  return guarded([&] {
+    REQUIRE(h && len, "pmaf_get_repulsive_track: NULL argument");
+    h->use_device();
+    sync(h);
+    const pmaf_planner::Track &t = h->trk;
+    const int P = h->D.P;
+    for (int p = 0; p < P; p++) len[p] = 0;
+    if (!t.on() || !t.d_pts) return;
+    h->download(len, t.d_len, P);
+    if (!track) return;
+    std::vector<double> pts((size_t)P * t.stride * 3);
+    h->download(pts.data(), t.d_pts, pts.size());
+    for (int p = 0; p < P; p++) {
+      REQUIRE(len[p] <= max_len, "pmaf_get_repulsive_track: max_len is shorter than a track");
+      std::memcpy(track + (size_t)p * max_len * 3, pts.data() + (size_t)p * t.stride * 3, sizeof(double) * 3 * (size_t)len[p]);
+    }
   });
 }
 
@@ -1167,6 +1351,8 @@ int pmaf_reset_agents(pmaf_planner *h, const double *pos, const double *vel, con
     // paths' first points); everything else is ordered by the stream
     for (auto &sl : h->x.slot)
       if (sl.pack_pending) { HIP_CHECK(hipEventSynchronize(sl.ev_pack)); sl.pack_pending = false; }
+    // coupled tracks: the reset below cuts every path to its first point, so the selected paths are taken here
+    if (h->trk.coupled) { capture_coupled_tracks(h); h->trk.captured = true; }
     ResidentGuard resident_guard{h};
     const double *live = stage_live_obstacles_zero_copy(h, obstacles);
     ManagerArgs A{};
@@ -1206,6 +1392,7 @@ int pmaf_tick(pmaf_planner *h, const double *obstacles, double dt, const double 
     const auto t_entry = std::chrono::steady_clock::now();
     h->use_device();
     require_drained(h, "pmaf_tick");
+    if (h->trk.on()) require_track_route(h, h->route, "pmaf_tick");   // (before anything is launched)
     // whatever fails between here and the manager kernel's result: the list handed over with this call may not have
     // reached D.obs_live, so it must not count as resident (a retry with the same list has to hand it over again)
     ResidentGuard resident_guard{h};

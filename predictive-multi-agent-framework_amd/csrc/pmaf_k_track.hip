@@ -1,0 +1,126 @@
+// pmaf_k_track.hip -- the repulsive track (include/pmaf.h "repulsive track"): k_rollout_w64_track, the one-slot
+// wave-per-agent rollout whose trailing repulsive obstacle follows a per-step track instead of o + k v dt, and
+// k_track_from_best, which copies a population's selected path into another population's track. A translation unit
+// and an object of its own: the other units' code objects do not move with it.
+//
+// The step is rollout_w64_body of pmaf_k_w64.hip, instantiated here -- and only here -- with TRACK = true (that file
+// is included for the body alone; its launcher and kernels are not compiled into this object). What TRACK adds to the
+// loop that carries code for the repulsive obstacle (SENT == 1, the obstacle in lane 60): one 24-byte load from a
+// wave-uniform address at the top of the step, for the step after it, and three selects behind the tail's
+// O.p += O.v dt that put the point into lane 60. The loop without code for the obstacle (SENT == 0) is the same
+// instantiation as in k_rollout_w64.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#define PMAF_W64_BODY_ONLY 1
+#include "pmaf_k_w64.hip"
+#include "pmaf_track.hpp"
+
+using namespace pmaf;
+
+// sentinel_reachable (pmaf_rollout_w64.hpp) for a track: can ANY point the rollout may read -- y_0 ... y_{min(L, cap) - 1},
+// the held last one included -- come into repelForce's range? The agent is never farther than steps * per_step from its
+// start (|a| <= 13, |v| <= vel_max, both clamped), whatever step a point belongs to, so a point farther than
+// range + reach from the start is out of range at every step. Same margins as sentinel_reachable; lanes stride over the
+// points. Conservative only: the loop it selects computes the same bits either way.
+__device__ __forceinline__ bool track_reachable(int lane, V3 p0, const double *trk, int n_pts, double zsent_lt,
+                                                const PopConst &C, int steps) {
+  const double adt = fabs(C.dt);
+  const double per_step = 6.5 * adt * adt + fabs(C.vel_max) * adt;
+  const double reach = (double)steps * per_step * 1.001 + 1e-9;
+  const double range = __builtin_sqrt(zsent_lt) * 1.001;
+  bool any = false;
+  for (int j = lane; j < n_pts; j += 64) {
+    const V3 y = mk(trk[3 * j], trk[3 * j + 1], trk[3 * j + 2]);
+    any = any || !(norm(p0 - y) > range + reach);   // NaN anywhere: keep testing
+  }
+  return wave_any(any);
+}
+
+template <bool DPPSUM, bool PLAIN>
+__global__ __launch_bounds__(64) void k_rollout_w64_track(DevView D, CostParams CP, TrackArgs T) {
+  constexpr int MATH = MATH_XACT;
+  const int lane = threadIdx.x;
+  const int pop = blockIdx.y;
+  const int a = blockIdx.x;  // grid.x == N
+  const int n_obs = D.n_obs, M = n_obs - 1;
+  const double *src = D.obs_start + (size_t)pop * 7 * n_obs;
+  const V3 p0 = mk(D.start_pos[pop * 3], D.start_pos[pop * 3 + 1], D.start_pos[pop * 3 + 2]);
+  const PopConst C0 = D.C;
+  // the population's track; a length of 0 (none attached, or the source population has no selection yet) leaves the
+  // obstacle on its straight line: rollout_w64_dispatch's decision and the body's untracked path
+  const int L = T.len[pop];
+  const double *trk = T.track + (size_t)pop * T.max_len * 3;
+  PMAF_BOUND(L >= 0 && L <= T.max_len);
+  bool reach;
+  if (L > 0) {
+    reach = track_reachable(lane, p0, trk, (L < D.cap) ? L : D.cap, D.zsent_lt[pop], C0, D.cap);
+  } else {
+    const V3 sp = mk(src[M], src[n_obs + M], src[2 * n_obs + M]);
+    const V3 sv = mk(src[3 * n_obs + M], src[4 * n_obs + M], src[5 * n_obs + M]);
+    reach = sentinel_reachable(p0, sp, sv, D.zsent_lt[pop], C0, D.cap);
+  }
+  // (as in rollout_w64_dispatch: field obstacles at rest with +0.0 velocities and the rel_vel rider's lane idle)
+  bool rest = true;
+  for (int i = lane; i < M; i += 64) {
+    const unsigned long long bx = (unsigned long long)__double_as_longlong(src[3 * n_obs + i]),
+                             by = (unsigned long long)__double_as_longlong(src[4 * n_obs + i]),
+                             bz = (unsigned long long)__double_as_longlong(src[5 * n_obs + i]);
+    rest = rest && ((bx | by | bz) == 0ull);
+  }
+  const bool st = !wave_any(!rest) && (M <= 59 || !reach);
+#define PMAF_BODY(T_) \
+  if (st) { \
+    if (!reach) rollout_w64_body<1, T_, MATH, 0, DPPSUM, PLAIN, true, false>(D, CP, lane, pop, a); \
+    else rollout_w64_body<1, T_, MATH, 1, DPPSUM, PLAIN, true, false, true>(D, CP, lane, pop, a, trk, L); \
+  } else if (!reach) rollout_w64_body<1, T_, MATH, 0, DPPSUM, PLAIN, false, false>(D, CP, lane, pop, a); \
+  else rollout_w64_body<1, T_, MATH, 1, DPPSUM, PLAIN, false, false, true>(D, CP, lane, pop, a, trk, L)
+  switch (D.types[a]) {
+    case T_GOAL: PMAF_BODY(T_GOAL); break;
+    case T_OBST: PMAF_BODY(T_OBST); break;
+    case T_GOALOBST: PMAF_BODY(T_GOALOBST); break;
+    case T_VEL: PMAF_BODY(T_VEL); break;
+    case T_RANDOM: PMAF_BODY(T_RANDOM); break;
+    case T_HAD: PMAF_BODY(T_HAD); break;
+    default: break;
+  }
+#undef PMAF_BODY
+}
+
+// One block per population; a population that is not coupled leaves its track (an uploaded one) alone.
+__global__ __launch_bounds__(64) void k_track_from_best(DevView D, CoupleArgs A) {
+  const int pop = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int q = A.src_pop[pop];
+  if (q < 0 || q >= D.P) return;
+  if (D.has_best[q] == 0) {
+    if (lane == 0) A.len[pop] = 0;
+    return;
+  }
+  int b = D.best_idx[q];
+  b = (b < 0) ? 0 : ((b >= D.N) ? D.N - 1 : b);
+  const size_t qa = (size_t)q * D.N + b;
+  int n = D.n_points[qa];
+  n = (n < 1) ? 1 : ((n > D.cap) ? D.cap : n);
+  const int first = (A.shift < n - 1) ? A.shift : (n - 1);
+  int len = n - first;   // == max(n - shift, 1)
+  if (len > A.max_len) len = A.max_len;
+  const double *src = A.paths + (qa * (size_t)D.cap + (size_t)first) * 3;
+  double *dst = A.track + (size_t)pop * A.max_len * 3;
+  for (int i = lane; i < 3 * len; i += 64) dst[i] = src[i];
+  if (lane == 0) A.len[pop] = len;
+}
+
+bool pmaf_k_launch_w64_track(const DevView &D, const CostParams &cp, const TrackArgs &T, bool dppsum, bool plain, size_t lds,
+                             hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+  const dim3 g64((unsigned)D.N, (unsigned)D.P), block(64);
+#define PMAF_L(K) hipExtLaunchKernelGGL(K, g64, block, (unsigned)lds, s, e0, e1, 0, D, cp, T)
+  if (dppsum) { if (plain) PMAF_L((k_rollout_w64_track<true, true>)); else PMAF_L((k_rollout_w64_track<true, false>)); }
+  else { if (plain) PMAF_L((k_rollout_w64_track<false, true>)); else PMAF_L((k_rollout_w64_track<false, false>)); }
+#undef PMAF_L
+  return true;
+}
+
+void pmaf_k_launch_track_from_best(const DevView &D, const CoupleArgs &A, hipStream_t s) {
+  hipLaunchKernelGGL(k_track_from_best, dim3((unsigned)D.P), dim3(64), 0, s, D, A);
+}

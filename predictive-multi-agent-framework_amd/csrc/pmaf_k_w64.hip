@@ -47,9 +47,15 @@ __device__ __forceinline__ auto w64_exp_consts(int lane) {
 // at 2 048 agents x 32 obstacles, profiles/r6_lpa_band.txt). With SLICE the two waves of a SIMD trade issue priority in
 // slices of the wall clock (the group kernel's scheme, pmaf_k_grp.hip) so that both finish together at 2 T / 1.42.
 // A template parameter, not a run-time flag: the one-wave-per-SIMD launches (C1, C2, C4) keep their step loop untouched.
-template <int TILES, int TYPE, int MATH, int SENT = 2, bool DPPSUM = false, bool PLAIN = false, bool STATICV = false, bool SLICE = false>
+// TRACK (pmaf_k_track.hip only: every kernel of this file's own launcher leaves it false): the repulsive obstacle follows
+// the population's repulsive track (include/pmaf.h "repulsive track") -- trk = its points [trk_len][3], trk_len == 0: no
+// track, the straight line as ever. One-slot kernel only; the loop without code for the obstacle (SENT == 0) never reads it.
+template <int TILES, int TYPE, int MATH, int SENT = 2, bool DPPSUM = false, bool PLAIN = false, bool STATICV = false, bool SLICE = false,
+          bool TRACK = false>
 __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostParams &CP, const int lane,
-                                                 const int pop, const int a) {
+                                                 const int pop, const int a, const double *trk = nullptr,
+                                                 const int trk_len = 0) {
+  static_assert(!TRACK || (TILES == 1 && SENT != 2), "the repulsive track rides in lane 60 of the one-slot kernel");
   extern __shared__ double smem[];
   const unsigned long long t_begin = wall_clock64();
   const int n_obs = D.n_obs;
@@ -94,6 +100,18 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
   V3 sent_p = mk(src[M], src[n_obs + M], src[2 * n_obs + M]);
   const V3 sent_v = mk(src[3 * n_obs + M], src[4 * n_obs + M], src[5 * n_obs + M]);
   const double sent_r = src[6 * n_obs + M];
+  // the track's first point is the obstacle of step 0 (y_0 in place of o_M); the pointer lives in a VGPR pair so that
+  // the per-step fetch below is ONE vector load from a wave-uniform address, like the path store, and not a scalar
+  // load on the LDS instructions' counter -- and it is a GLOBAL pointer (the pin alone would leave a generic one: flat
+  // loads, which count on that counter as well)
+  typedef const __attribute__((address_space(1))) double *gptr;
+  gptr trk_v = (gptr)trk;
+  const int trk_last = (trk_len > 0) ? (trk_len - 1) : 0;
+  const lmask trk_m = (TRACK && SENT == 1 && trk_len > 0) ? (1ull << 60) : 0ull;
+  if (TRACK && SENT == 1) {
+    asm volatile("" : "+v"(trk_v));
+    if (trk_len > 0) sent_p = mk(trk_v[0], trk_v[1], trk_v[2]);
+  }
 
   V3 goal = mk(D.goal[pop * 3], D.goal[pop * 3 + 1], D.goal[pop * 3 + 2]);
   V3 init_pos = mk(D.agent_init_pos[pop * 3], D.agent_init_pos[pop * 3 + 1], D.agent_init_pos[pop * 3 + 2]);
@@ -190,6 +208,13 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
   while ((dg > 0.1) && (n < D.cap)) {  // wave-uniform guard, B/src/cf_agent.cpp:310-311
     unsigned long long clk = 0ull;
     if (SLICE) clk = wall_clock64();
+    // repulsive track: the point of the COMING step (step n, held at the last one) is requested here, a whole step ahead
+    // of the tail that consumes it
+    V3 trk_next = mk(0.0, 0.0, 0.0);
+    if (TRACK && SENT == 1) {
+      const gptr tp = trk_v + 3 * ((n < trk_last) ? n : trk_last);
+      trk_next = mk(tp[0], tp[1], tp[2]);
+    }
     // gate, :315-317
     // |v| < 0.5 vmax and |p - init| < 0.2 on exact squared thresholds
     // (as a lane mask built from single compares: pmaf_rollout_w64.hpp, "lane predicates as masks")
@@ -250,6 +275,10 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
     // (one slot per lane: unconditionally -- for obstacles at rest every further application is the identity, and
     // three multiply-adds are cheaper than a branch in the middle of the tail)
     if (PRE) O.p[0] = O.p[0] + O.v[0] * C.dt;
+    if (TRACK && SENT == 1) {   // lane 60 takes the track's point in place of o + v dt (three selects, no masked block)
+      const bool tl = PMAF_LANE(trk_m);
+      O.p[0].x = tl ? trk_next.x : O.p[0].x; O.p[0].y = tl ? trk_next.y : O.p[0].y; O.p[0].z = tl ? trk_next.z : O.p[0].z;
+    }
     {
       // ONE sqrt / reciprocal / divide sequence for the whole tail: lane 63 goal distance and direction (|g|,
       // g.normalized()), lane 62 the speed clamp (|nv|, vel_max / |nv|), lane 61 attractorForce's limit
@@ -429,6 +458,8 @@ __global__ __launch_bounds__(64) void k_rollout_w64_sliced(DevView D, CostParams
 }
 
 
+// PMAF_W64_BODY_ONLY (pmaf_k_track.hip includes this file for rollout_w64_body): no kernel launcher below
+#ifndef PMAF_W64_BODY_ONLY
 #ifndef PMAF_W64_MATH
 #error "compile with -DPMAF_W64_MATH=0|1|2|3"
 #endif
@@ -467,3 +498,4 @@ bool PMAF_W64_LAUNCH(const DevView &D, const CostParams &cp, int tiles, bool dpp
 #undef PMAF_L
   return false;
 }
+#endif  // PMAF_W64_BODY_ONLY

@@ -42,6 +42,10 @@ struct Input {
   int mw_lds_kb = 0;            // PMAF_MW_LDS_KB: the multi-wave launcher's LDS request (0: its placement rule)
   bool dpp_sum = true;          // PMAF_SUM=dpp|lds: the one-slot wave-per-agent kernels' ordered force sum
   bool w64_slice = true;        // PMAF_W64_SLICE=0|1: the priority-slicing loop where the rule below offers it
+  // a repulsive track is attached or the populations are coupled (include/pmaf.h "repulsive track"). It changes none of
+  // the fields the rule decides -- a handle is never moved to another kernel family for its track --; Route::carries_track
+  // says whether the launch the route names has the variant that follows one (pmaf_k_track.hip)
+  bool tracked = false;
 };
 
 struct Route {
@@ -59,7 +63,18 @@ struct Route {
   bool tuned_real_step = false; // ManagerArgs::tuned_real_step
   int n_blocks = 1;             // blocks per population of the GROUP / GENERIC grid (and of k_plan_steps)
   size_t lds_rollout = 0;       // dynamic LDS of the one-wave rollout launch (and of k_plan_steps), bytes
+  bool carries_track = false;   // the routed launch exists as k_rollout_w64_track (whatever Input::tracked says)
 };
+
+static inline const char *family_name(Family f) {
+  switch (f) {
+    case EXTERNAL: return "external";
+    case MULTI_WAVE: return "multi-wave";
+    case WAVE_PER_AGENT: return "wave-per-agent";
+    case GROUP: return "group";
+    default: return "generic";
+  }
+}
 
 // The mapping with the smallest estimated kernel time (pmaf_lpa_model.hpp: a table of measured launch times per
 // mapping, obstacle slots per lane and waves per SIMD; profiles/r6_lpa_grid.txt). History of the rule it replaces:
@@ -175,6 +190,10 @@ static inline Route route(const Input &in) {
   // object -- the product kernel's own assembly with delay instructions inserted -- on the wave-per-agent grid with
   // lds_rollout; the other figures stay what the handle reported without it
   if (in.external) r.family = EXTERNAL;
+
+  // ---- the repulsive track: k_rollout_w64_track is the one-slot wave-per-agent kernel (both ordered sums, PLAIN and
+  // general step) of the default arithmetic policy, without the priority-slicing loop
+  r.carries_track = r.family == WAVE_PER_AGENT && r.slots == 1 && r.tiles == 1 && in.math == pmaf::MATH_XACT && !r.sliced;
   return r;
 }
 

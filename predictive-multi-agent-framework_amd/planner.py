@@ -78,6 +78,9 @@ SYMBOLS = {
     "pmaf_select_clear_tracks": (C.c_int, [_V, C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _dp,
                                            C.c_double, C.c_double, _ip, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip,
                                            _dp, _ip]),
+    "pmaf_set_repulsive_track": (C.c_int, [_V, _dp, _ip, C.c_int32]),
+    "pmaf_couple_tracks": (C.c_int, [_V, _ip, C.c_int32]),
+    "pmaf_get_repulsive_track": (C.c_int, [_V, _dp, _ip, C.c_int32]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -752,6 +755,44 @@ class PmafPlanner:
         """measurement tooling: run the rollout launches out of an external code object (None: built-in again)"""
         self._chk(self.L.pmaf_debug_external_rollout(
             self._h, code_object_path.encode() if code_object_path else None, kernel_name.encode() if kernel_name else None))
+
+    # -- repulsive track (include/pmaf.h "repulsive track") --
+    def set_repulsive_track(self, tracks, lengths=None):
+        """tracks: None (detach), one [L][3] array (single population), or a sequence of P entries, each [L_p][3] or None;
+        or -- with lengths [P] -- a padded [P][max_len][3] array handed over as it is"""
+        if tracks is None:
+            self._chk(self.L.pmaf_set_repulsive_track(self._h, None, None, 0))
+            return
+        if lengths is not None:
+            buf = _d(tracks).reshape(self.P, -1, 3)
+            ln = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.int32), (self.P,)))
+        else:
+            if self.P == 1 and not isinstance(tracks, (list, tuple)):
+                tracks = [tracks]
+            assert len(tracks) == self.P
+            tr = [np.zeros((0, 3)) if t is None else _d(t).reshape(-1, 3) for t in tracks]
+            ln = np.array([len(t) for t in tr], dtype=np.int32)
+            buf = np.zeros((self.P, max(1, int(ln.max())), 3))
+            for p, t in enumerate(tr):
+                buf[p, :len(t)] = t
+        self._chk(self.L.pmaf_set_repulsive_track(self._h, _p(buf), _pi(ln), int(buf.shape[1])))
+
+    def couple_tracks(self, src_pop, shift=0):
+        """src_pop [P] (-1: none) or None to uncouple: population p follows the selected path of population src_pop[p]"""
+        if src_pop is None:
+            self._chk(self.L.pmaf_couple_tracks(self._h, None, 0))
+            return
+        src = np.ascontiguousarray(np.broadcast_to(np.asarray(src_pop, dtype=np.int32), (self.P,)))
+        self._chk(self.L.pmaf_couple_tracks(self._h, _pi(src), int(shift)))
+
+    def get_repulsive_track(self):
+        """the tracks the last launched rollout used: a list of P arrays [L_p][3] (L_p == 0: none)"""
+        ln = np.zeros(self.P, dtype=np.int32)
+        self._chk(self.L.pmaf_get_repulsive_track(self._h, None, _pi(ln), 0))
+        m = max(1, int(ln.max()))
+        buf = np.zeros((self.P, m, 3))
+        self._chk(self.L.pmaf_get_repulsive_track(self._h, _p(buf), _pi(ln), m))
+        return [buf[p, :ln[p]].copy() for p in range(self.P)]
 
     def launch_config(self):
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)

@@ -136,7 +136,7 @@ class DualArmCoupling:
         return obs
 
     def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None, adopt=False,
-                  clear=None):
+                  clear=None, tracks=None):
         """One tick of both arms as populations 0 / 1 of ONE handle, the two winners picked TOGETHER: the node's
         five-call sequence with pmaf_select_pair in it (include/pmaf.h "cross audit") --
         stop -> evaluate -> select_pair -> move_real(agent_id = the pair) -> reset -> start. The pair is the cheapest
@@ -154,8 +154,15 @@ class DualArmCoupling:
         `horizon` points of both paths (pmaf_select_pair_clear, include/pmaf.h "joint selection"): each arm's trailing
         sphere at the other arm's last set-point is left to the cross audit (skip_trailing), the previous tick's pair is
         the hysteresis reference, and adopt is carried out by the same call. The dict is select_pair_clear's plus
-        feasible (rule 0 or 1) and positions. None: as before."""
+        feasible (rule 0 or 1) and positions. None: as before.
+        tracks = shift: the rollouts this tick starts follow the other arm's selected path from point `shift` on instead of
+        the sphere at rest (pmaf_couple_tracks, include/pmaf.h "repulsive track"; with adopt=True the pair's paths, else
+        evaluate's own selections). coupled_obstacles is left as it is: the sphere at the last set-point stays in the
+        live list for the real step. The coupling stays on the handle until planner.couple_tracks(None). None: as before."""
         assert planner.P == 2, "pair_tick drives the two populations of one handle"
+        if tracks is not None and getattr(self, "_track_shift", None) != int(tracks):
+            planner.couple_tracks([1, 0], int(tracks))
+            self._track_shift = int(tracks)
         planner.stop()
         best = planner.evaluate(cost_gains, ws)
         if clear is not None:
