@@ -24,7 +24,13 @@
 #                        (tests/test_sentinel_track.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
-#   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API)
+#   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API): handle, tick protocol, repulsive track,
+#                        stepping API, getters; with three units of its own for what pmaf_tick does not run --
+#   pmaf_host_audit.cpp    the path audit, the selections, the cross audit, the link force
+#   pmaf_host_exchange.cpp the winner-record exchange and the peer mailboxes
+#   pmaf_host_state.cpp    checkpointing
+#                        (they share pmaf_host_impl.hpp: the handle, its owning buffers, the bounded wait; host units only,
+#                        not in DEPS_K; the host objects are compiled on every build)
 #   pmaf_shard.cpp       communicators + the winner-record exchange (RCCL / host-callback)
 # linked with -lamdhip64 -lrccl.
 #
@@ -113,10 +119,11 @@ kcompile pairclear pmaf_k_pairclear.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
 # (the flags of k_w64_m2_t1: the same body)
 kcompile track pmaf_k_track.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
-( $CXX $HFLAGS -c pmaf_host.cpp -o "$OBJ/host.o" 2> "$OBJ/host.log" ) &
-pids+=($!); names+=("host")
-( $CXX $HFLAGS -c pmaf_shard.cpp -o "$OBJ/shard.o" 2> "$OBJ/shard.log" ) &
-pids+=($!); names+=("shard")
+HOST_UNITS="host host_audit host_exchange host_state shard"   # pmaf_<unit>.cpp -> <unit>.o, all with HFLAGS
+for u in $HOST_UNITS; do
+  ( $CXX $HFLAGS -c "pmaf_$u.cpp" -o "$OBJ/$u.o" 2> "$OBJ/$u.log" ) &
+  pids+=($!); names+=("$u")
+done
 fail=0
 for i in "${!pids[@]}"; do
   if ! wait "${pids[$i]}"; then echo "compile failed: ${names[$i]}" >&2; cat "$OBJ/${names[$i]}.log" >&2; fail=1; fi
@@ -126,7 +133,7 @@ printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
   "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o \
-  "$OBJ"/host.o "$OBJ"/shard.o -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
+  $(for u in $HOST_UNITS; do echo "$OBJ/$u.o"; done) -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
 cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

@@ -1,5 +1,5 @@
 // pmaf_comm.hpp -- internal view of a communicator (include/pmaf.h: pmaf_comm) shared by pmaf_shard.cpp (which owns
-// it) and pmaf_host.cpp (the winner-record exchange).
+// it) and pmaf_host_exchange.cpp (the winner-record exchange).
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -1,7 +1,7 @@
 // Which rollout kernel a handle launches, and with what: ONE pure function from everything the choice depends on
 // (Input) to everything the host forwards (Route). Host-only like pmaf_lpa_model.hpp: no HIP call, no getenv, no handle;
-// no kernel translation unit includes it. pmaf_host.cpp keeps an Input and the Route computed from it per handle and
-// recomputes the Route (reroute) where an input changes: at create, where the gains / the mass enter the handle
+// no kernel translation unit includes it. The handle (pmaf_host_impl.hpp) keeps an Input and the Route computed from it,
+// and pmaf_host.cpp recomputes the Route (reroute) where an input changes: at create, where the gains / the mass enter the handle
 // (refresh_plain_step), when an external kernel is loaded or unloaded, and when the multi-wave launcher refuses.
 // tests/test_route.py drives this header alone (tests/cpp/route_table.cpp): the families, the boundaries of every rule
 // and the invariants between the fields, without a device.

@@ -3,7 +3,7 @@
 // (SURVEY.md 8e). Two transports behind one handle:
 //   * RCCL: ncclAllGather over xGMI on device buffers, enqueued on a HIP stream (the product path between GPUs);
 //   * host callback: the caller's CPU all-gather (MPI, gloo, tests), staged through pinned host memory.
-// The exchange itself (what is packed, when it is enqueued) lives in pmaf_host.cpp.
+// The exchange itself (what is packed, when it is enqueued) lives in pmaf_host_exchange.cpp.
 #include <rccl/rccl.h>
 
 #include <cstdio>
