@@ -724,6 +724,43 @@ class CfManager {
     check(pmaf_set_repulsive_track(h_, track.empty() ? nullptr : pts.data(), &len, len > 0 ? len : 1), "setRepulsiveTrack");
   }
 
+  // The rollouts started from now on see the FIELD obstacles on predicted tracks instead of their straight lines o + k v dt
+  // (pmaf_set_obstacle_tracks, include/pmaf.h "obstacle tracks"; no reference equivalent): at prediction step k obstacle i
+  // has the position and the velocity of per_step[min(first + k, size - 1)][i], held at the end. Each inner list holds the
+  // M field obstacles in the creation list's order, or M + 1 with the last (the repulsive obstacle: setRepulsiveTrack)
+  // ignored; the radii stay the creation list's. An empty list detaches. The live list keeps steering the real step and
+  // the audits. std::runtime_error where the handle's rollout kernel cannot follow tracks (more than 60 field obstacles,
+  // another arithmetic policy), std::invalid_argument on a list of another size.
+  void setObstacleTracks(const std::vector<std::vector<Obstacle>> &per_step, int first = 0) {
+    require();
+    const size_t M = (size_t)n_obs_ - 1;
+    std::vector<double> pts;
+    pts.reserve(per_step.size() * M * 6);
+    for (const std::vector<Obstacle> &step : per_step) {
+      if (step.size() != M && step.size() != M + 1) throw std::invalid_argument("setObstacleTracks: every step needs the M field obstacles");
+      for (size_t i = 0; i < M; ++i) {
+        const Vector3d p = step[i].getPosition(), v = step[i].getVelocity();
+        pts.insert(pts.end(), {p.x(), p.y(), p.z(), v.x(), v.y(), v.z()});
+      }
+    }
+    const int32_t len = (int32_t)per_step.size();
+    check(pmaf_set_obstacle_tracks(h_, per_step.empty() ? nullptr : pts.data(), &len, len > 0 ? len : 1), "setObstacleTracks");
+    if (len > 0 && first != 0) {
+      const int32_t f = first;
+      check(pmaf_set_obstacle_track_offset(h_, &f), "setObstacleTracks");
+    }
+  }
+
+  // A closed loop that keeps following the same prediction: the tracks' offset moves on by `by` points (one per tick)
+  // without another upload (pmaf_set_obstacle_track_offset).
+  void advanceObstacleTracks(int by = 1) {
+    require();
+    int32_t len = 0, first = 0;
+    check(pmaf_get_obstacle_tracks(h_, nullptr, &len, &first, 0), "advanceObstacleTracks");
+    first += by;
+    check(pmaf_set_obstacle_track_offset(h_, &first), "advanceObstacleTracks");
+  }
+
   // ---- synchronous stepping API (no callers in the reference; B/src/cf_manager.cpp:220-224, 238-244, 265-291) ----
   // Deviation: after any of these calls startPrediction() needs a resetEEAgents() / setInitialPosition() first
   // (std::runtime_error otherwise): rollouts start from the population's reset state, the reference's threads would

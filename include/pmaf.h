@@ -554,6 +554,44 @@ int pmaf_set_repulsive_track(pmaf_planner *h, const double *track, const int32_t
 int pmaf_couple_tracks(pmaf_planner *h, const int32_t *src_pop, int32_t shift);
 int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32_t max_len);
 
+/* ---- obstacle tracks: rollouts that follow predicted tracks of the field obstacles (exports added under ABI 7) ----
+ * A rollout sees every circular-field obstacle on the straight line o_i + k v_i dt (predictObstacles,
+ * B/src/cf_agent.cpp:270-276). A sphere that turns round, a tracked human arm, the links of the other arm along its
+ * selected path all leave that line. A population p may therefore have obstacle tracks: L >= 1 points, each point the
+ * state of all M field obstacles -- six doubles per obstacle: position, velocity -- and an offset first >= 0. While it
+ * has them, every rollout of p changes in one way: at prediction step k (k = 0 is the step from the start state) field
+ * obstacle i has the position AND the velocity of point min(first + k, L-1), both taken verbatim and both held at the
+ * end, instead of the iterated o_i + k v_i dt with the constant v_i. Nothing else changes: the radii are the creation
+ * list's radii; the trailing obstacle stays on its line, or on its repulsive track if the population has one (the two
+ * kinds of track may be attached together); the latch, known, min_obs_dist, scoring, the real step, pmaf_move_real, the
+ * stepping API and the audits see the live list as ever. L == 0: no tracks, the population behaves exactly as without
+ * these calls. Tracks whose points are the iterated straight lines with the constant velocities give bit-identical
+ * rollouts. Points of index >= first + max_prediction_steps are never read. No reference equivalent. Tracks are
+ * inputs, not planner state: pmaf_save_state blobs do not hold them.
+ * Route. As for the repulsive track: the variant that follows obstacle tracks (k_rollout_w64_ftrack, which also follows
+ * a repulsive track) exists for the one-slot wave-per-agent kernel of the default arithmetic policy. On any other
+ * route pmaf_set_obstacle_tracks returns PMAF_ERR_STATE with a message naming the route, and so do pmaf_start /
+ * pmaf_tick when the route became unsupported after the attach. A handle with only a repulsive track, and every
+ * handle without tracks, launches what it launched before these calls existed.
+ * Limits: no tracks on the multi-slot (> 60 field obstacles), multi-wave, group, sliced and generic routes, nor under
+ * the other arithmetic policies; the audits and the selections keep the live list's straight lines -- they do not see
+ * the tracks; the tracks come from the host only (no device-side source like pmaf_couple_tracks); the planner node
+ * (planner_node.h) does not use them.
+ * pmaf_set_obstacle_tracks: tracks [P][max_len][M][6] (M = n_obstacles - 1; x y z vx vy vz), len [P]; takes effect from
+ *   the next pmaf_start / pmaf_tick and stays until replaced; every population's offset becomes 0. tracks == NULL,
+ *   len == NULL or every len == 0 detaches. A value inside len that is NaN or outside the supported numeric range,
+ *   len < 0 or len > max_len: PMAF_ERR_INVALID. Waits for a running rollout as the setters do; the upload runs in
+ *   stream order on the handle's stream into a grow-only device buffer (transposed on the host so that a wave's load
+ *   of one component is contiguous).
+ * pmaf_set_obstacle_track_offset: first [P], each >= 0 (PMAF_ERR_INVALID otherwise): a closed loop that advances
+ *   along the same prediction by one point per tick uploads P integers instead of the tracks. PMAF_ERR_STATE while no
+ *   tracks are attached.
+ * pmaf_get_obstacle_tracks: what the last launched rollout used (waits for it): len [P], first [P] (may be NULL) and
+ *   -- tracks != NULL -- tracks [P][max_len][M][6]; PMAF_ERR_INVALID when max_len is shorter than one of them. */
+int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len);
+int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first);
+int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len);
+
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last
  * obstacle at n link points. link_pos [n][3], k_r_force [n], out [n][3]. */

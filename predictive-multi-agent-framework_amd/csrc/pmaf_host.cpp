@@ -1,5 +1,5 @@
 // pmaf_host.cpp -- host side of libpmaf_hip.so: the C-ABI of include/pmaf.h (handle, buffers, streams, the tick
-// protocol, the repulsive track, the stepping API, getters, profiling) over the kernels of pmaf_k_*.hip (launch
+// protocol, the repulsive track and the obstacle tracks, the stepping API, getters, profiling) over the kernels of pmaf_k_*.hip (launch
 // interface: pmaf_types.hpp). The path audit and the selections: pmaf_host_audit.cpp; the winner-record exchange and
 // the peer mailboxes: pmaf_host_exchange.cpp; checkpointing: pmaf_host_state.cpp (shared: pmaf_host_impl.hpp).
 // Plain C++ against the HIP runtime API; there is no CPU fallback in this library.
@@ -114,6 +114,13 @@ static bool dispatch_rollout(pmaf_planner *h, hipEvent_t e0, hipEvent_t e1) {
       reroute(h);
       return dispatch_rollout(h, e0, e1);
     case pmaf_route::WAVE_PER_AGENT:
+      if (h->ftrk.on()) {   // (launch_rollout has checked Route::carries_field_tracks)
+        const pmaf_planner::FieldTrack &f = h->ftrk;
+        const TrackArgs T = h->trk.on() ? TrackArgs{h->trk.d_pts.get(), h->trk.d_len.get(), h->trk.stride}
+                                        : TrackArgs{f.d_no_pts.get(), f.d_no_len.get(), 1};
+        const FTrackArgs F{f.d_pts.get(), f.d_len.get(), f.d_first.get(), f.stride};
+        return pmaf_k_launch_w64_ftrack(h->D, h->cp, T, F, r.dpp_sum, r.plain, r.lds_rollout, h->stream, e0, e1);
+      }
       if (h->trk.on()) {   // (launch_rollout has checked Route::carries_track)
         const TrackArgs T{h->trk.d_pts.get(), h->trk.d_len.get(), h->trk.stride};
         return pmaf_k_launch_w64_track(h->D, h->cp, T, r.dpp_sum, r.plain, r.lds_rollout, h->stream, e0, e1);
@@ -128,9 +135,10 @@ static bool dispatch_rollout(pmaf_planner *h, hipEvent_t e0, hipEvent_t e1) {
 }
 
 // A track is never silently ignored: the launch the route names must have the variant that follows it.
-static void require_track_route(const pmaf_planner *h, const pmaf_route::Route &r, const char *who) {
-  if (r.carries_track) return;
-  fail(PMAF_ERR_STATE, std::string(who) + ": the repulsive track needs the one-slot wave-per-agent kernel of the default arithmetic "
+enum TrackKind { REPULSIVE_TRACK, FIELD_TRACKS };
+static void require_track_route(const pmaf_planner *h, const pmaf_route::Route &r, const char *who, TrackKind kind = REPULSIVE_TRACK) {
+  if (kind == FIELD_TRACKS ? r.carries_field_tracks : r.carries_track) return;
+  fail(PMAF_ERR_STATE, std::string(who) + (kind == FIELD_TRACKS ? ": the obstacle tracks need" : ": the repulsive track needs") + " the one-slot wave-per-agent kernel of the default arithmetic "
        "policy (<= 60 field obstacles, one wave per SIMD at most); this handle's route is the " + pmaf_route::family_name(r.family) +
        " kernel" + (r.family == pmaf_route::WAVE_PER_AGENT ? (r.sliced ? " with the priority-slicing loop" : r.slots > 1 ?
        " with several obstacle slots per lane" : " of another arithmetic policy") : ""));
@@ -168,6 +176,7 @@ static void capture_coupled_tracks(pmaf_planner *h) {
 }
 
 static void launch_rollout(pmaf_planner *h) {
+  if (h->ftrk.on()) require_track_route(h, h->route, "rollout launch", FIELD_TRACKS);
   if (h->trk.on()) {
     require_track_route(h, h->route, "rollout launch");   // (pmaf_start / pmaf_tick have checked already)
     // before this rollout overwrites the paths -- unless a reset in front of it already has, and took them first
@@ -645,6 +654,7 @@ int pmaf_start(pmaf_planner *h) {
     // (guard B/src/cf_agent.cpp:310-311 is already false)
     if (!h->rollout_pending) return;
     if (h->trk.on()) require_track_route(h, h->route, "pmaf_start");
+    if (h->ftrk.on()) require_track_route(h, h->route, "pmaf_start", FIELD_TRACKS);
     if (!h->cp_valid) {  // no evaluate yet: score with neutral workspace terms, rescored on evaluate
       h->cp = CostParams{};
       h->cp.ws[0] = h->cp.ws[2] = h->cp.ws[4] = INFINITY;
@@ -659,13 +669,14 @@ int pmaf_start(pmaf_planner *h) {
 
 // ---- repulsive track ----
 // attach / detach: the route's `tracked` input follows, and an attach the routed launch cannot carry is refused here
-static void set_tracked(pmaf_planner *h, bool want, const char *who) {
+static void set_tracked(pmaf_planner *h, bool want, const char *who, TrackKind kind = REPULSIVE_TRACK) {
+  bool pmaf_route::Input::*flag = (kind == FIELD_TRACKS) ? &pmaf_route::Input::field_tracked : &pmaf_route::Input::tracked;
   if (want) {
     pmaf_route::Input in = h->route_in;
-    in.tracked = true;
-    require_track_route(h, pmaf_route::route(in), who);
+    in.*flag = true;
+    require_track_route(h, pmaf_route::route(in), who, kind);
   }
-  h->route_in.tracked = want;
+  h->route_in.*flag = want;
   reroute(h);
 }
 
@@ -752,6 +763,98 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
     for (int p = 0; p < P; p++) {
       REQUIRE(len[p] <= max_len, "pmaf_get_repulsive_track: max_len is shorter than a track");
       std::memcpy(track + (size_t)p * max_len * 3, pts.data() + (size_t)p * t.stride * 3, sizeof(double) * 3 * (size_t)len[p]);
+    }
+  });
+}
+
+// ---- obstacle tracks ----
+int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len) {
+  return guarded([&] {
+    REQUIRE(h, "pmaf_set_obstacle_tracks: NULL handle");
+    h->use_device();
+    require_drained(h, "pmaf_set_obstacle_tracks");
+    pmaf_planner::FieldTrack &f = h->ftrk;
+    const int P = h->D.P, M = h->D.n_obs - 1;
+    bool any = false;
+    if (tracks && len) {
+      REQUIRE(max_len >= 1, "pmaf_set_obstacle_tracks: max_len must be >= 1");
+      for (int p = 0; p < P; p++) {
+        REQUIRE(len[p] >= 0 && len[p] <= max_len, "pmaf_set_obstacle_tracks: need 0 <= len <= max_len");
+        check_range(tracks + (size_t)p * max_len * M * 6, (size_t)len[p] * M * 6, "pmaf_set_obstacle_tracks: tracks");
+        any = any || len[p] > 0;
+      }
+    }
+    if (any) set_tracked(h, true, "pmaf_set_obstacle_tracks", FIELD_TRACKS);
+    sync(h);   // a running rollout still reads the buffers
+    f.attached = any;
+    f.first.assign(P, 0);
+    f.len.assign(P, 0);
+    if (!any) {
+      set_tracked(h, false, "pmaf_set_obstacle_tracks", FIELD_TRACKS);
+      if (f.d_len.get()) {   // (the getter reads them)
+        h->upload(f.d_len.get(), f.len.data(), (size_t)P);
+        h->upload(f.d_first.get(), f.first.data(), (size_t)P);
+      }
+      return;
+    }
+    for (int p = 0; p < P; p++) f.len[p] = len[p];
+    // the device layout (pmaf_ftrack.hpp): [P][stride][6][64], transposed here; a population's points lie at its own
+    // stride, so a shorter upload into a grown buffer leaves the tail of the longer one behind it, never read
+    if (f.d_pts.reserve(sizeof(double) * (size_t)P * std::max(f.stride, (int)max_len) * PMAF_FTRACK_POINT)) f.stride = std::max(f.stride, (int)max_len);
+    f.d_len.reserve(sizeof(int32_t) * P);
+    f.d_first.reserve(sizeof(int32_t) * P);
+    if (f.d_no_pts.reserve(sizeof(double) * (size_t)P * 3)) HIP_CHECK(hipMemsetAsync(f.d_no_pts.get(), 0, sizeof(double) * (size_t)P * 3, h->stream));
+    if (f.d_no_len.reserve(sizeof(int32_t) * P)) HIP_CHECK(hipMemsetAsync(f.d_no_len.get(), 0, sizeof(int32_t) * P, h->stream));
+    std::vector<double> pts((size_t)P * f.stride * PMAF_FTRACK_POINT, 0.0);
+    for (int p = 0; p < P; p++)
+      for (int k = 0; k < f.len[p]; k++) {
+        const double *src = tracks + ((size_t)p * max_len + k) * M * 6;
+        double *dst = pts.data() + ((size_t)p * f.stride + k) * PMAF_FTRACK_POINT;
+        for (int i = 0; i < M; i++)
+          for (int c = 0; c < 6; c++) dst[c * PMAF_FTRACK_LANES + i] = src[i * 6 + c];
+      }
+    h->upload(f.d_pts.get(), pts.data(), pts.size());
+    h->upload(f.d_len.get(), f.len.data(), (size_t)P);
+    h->upload(f.d_first.get(), f.first.data(), (size_t)P);
+  });
+}
+
+int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first) {
+  return guarded([&] {
+    REQUIRE(h && first, "pmaf_set_obstacle_track_offset: NULL argument");
+    h->use_device();
+    require_drained(h, "pmaf_set_obstacle_track_offset");
+    pmaf_planner::FieldTrack &f = h->ftrk;
+    const int P = h->D.P;
+    for (int p = 0; p < P; p++) REQUIRE(first[p] >= 0, "pmaf_set_obstacle_track_offset: first must be >= 0");
+    if (!f.on()) fail(PMAF_ERR_STATE, "pmaf_set_obstacle_track_offset: no obstacle tracks are attached (pmaf_set_obstacle_tracks)");
+    f.first.assign(first, first + P);
+    h->upload(f.d_first.get(), f.first.data(), (size_t)P);   // (stream order: behind a running rollout)
+  });
+}
+
+int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len) {
+  return guarded([&] {
+    REQUIRE(h && len, "pmaf_get_obstacle_tracks: NULL argument");
+    h->use_device();
+    sync(h);
+    const pmaf_planner::FieldTrack &f = h->ftrk;
+    const int P = h->D.P, M = h->D.n_obs - 1;
+    for (int p = 0; p < P; p++) { len[p] = 0; if (first) first[p] = 0; }
+    if (!f.on() || !f.d_pts.get()) return;
+    h->download(len, f.d_len.get(), P);
+    if (first) h->download(first, f.d_first.get(), P);
+    if (!tracks) return;
+    std::vector<double> pts((size_t)P * f.stride * PMAF_FTRACK_POINT);
+    h->download(pts.data(), f.d_pts.get(), pts.size());
+    for (int p = 0; p < P; p++) {
+      REQUIRE(len[p] <= max_len, "pmaf_get_obstacle_tracks: max_len is shorter than a population's tracks");
+      for (int k = 0; k < len[p]; k++) {
+        const double *src = pts.data() + ((size_t)p * f.stride + k) * PMAF_FTRACK_POINT;
+        double *dst = tracks + ((size_t)p * max_len + k) * M * 6;
+        for (int i = 0; i < M; i++)
+          for (int c = 0; c < 6; c++) dst[i * 6 + c] = src[c * PMAF_FTRACK_LANES + i];
+      }
     }
   });
 }
@@ -894,6 +997,7 @@ int pmaf_tick(pmaf_planner *h, const double *obstacles, double dt, const double 
     h->use_device();
     require_drained(h, "pmaf_tick");
     if (h->trk.on()) require_track_route(h, h->route, "pmaf_tick");   // (before anything is launched)
+    if (h->ftrk.on()) require_track_route(h, h->route, "pmaf_tick", FIELD_TRACKS);
     // whatever fails between here and the manager kernel's result: the list handed over with this call may not have
     // reached D.obs_live, so it must not count as resident (a retry with the same list has to hand it over again)
     ResidentGuard resident_guard{h};

@@ -22,6 +22,7 @@
 #include "pmaf_lpa_model.hpp"
 #include "pmaf_route.hpp"
 #include "pmaf_track.hpp"
+#include "pmaf_ftrack.hpp"
 
 using namespace pmaf;
 
@@ -272,6 +273,18 @@ struct pmaf_planner {
     int shift = 0;
     bool on() const { return uploaded || coupled; }
   } trk;
+  // ---- obstacle tracks (include/pmaf.h "obstacle tracks"): inputs like the repulsive track, not in the checkpoint blob.
+  // d_pts [P][stride][6][64] (pmaf_ftrack.hpp; grow-only), d_len / d_first [P]: what the next rollout launch follows. The
+  // host keeps the lengths and offsets (the refusals and the detach need them), never the points. d_no_pts / d_no_len: the
+  // one-point, zero-length repulsive track k_rollout_w64_ftrack is handed while the handle has no repulsive track.
+  struct FieldTrack {
+    DeviceBuf<double> d_pts, d_no_pts;
+    DeviceBuf<int32_t> d_len, d_first, d_no_len;
+    int stride = 0;                               // points per population the device buffer holds (>= 1 once allocated)
+    std::vector<int32_t> len, first;
+    bool attached = false;                        // some len > 0
+    bool on() const { return attached; }
+  } ftrk;
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]
   CostParams cp{};

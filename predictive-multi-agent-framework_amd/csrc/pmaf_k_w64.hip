@@ -50,12 +50,18 @@ __device__ __forceinline__ auto w64_exp_consts(int lane) {
 // TRACK (pmaf_k_track.hip only: every kernel of this file's own launcher leaves it false): the repulsive obstacle follows
 // the population's repulsive track (include/pmaf.h "repulsive track") -- trk = its points [trk_len][3], trk_len == 0: no
 // track, the straight line as ever. One-slot kernel only; the loop without code for the obstacle (SENT == 0) never reads it.
+// FTRACK (pmaf_k_ftrack.hip only, together with TRACK): the field obstacles follow the population's obstacle tracks
+// (include/pmaf.h "obstacle tracks") -- ftrk = its points [ftrk_len][6][64] (position and velocity, one obstacle per lane:
+// the six loads of a step are contiguous across the lanes), ftrk_first = the offset; ftrk_len == 0: none, the straight
+// lines as ever. One-slot kernel, never the STATICV bodies: a tracked obstacle moves whatever the live list says.
 template <int TILES, int TYPE, int MATH, int SENT = 2, bool DPPSUM = false, bool PLAIN = false, bool STATICV = false, bool SLICE = false,
-          bool TRACK = false>
+          bool TRACK = false, bool FTRACK = false>
 __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostParams &CP, const int lane,
                                                  const int pop, const int a, const double *trk = nullptr,
-                                                 const int trk_len = 0) {
+                                                 const int trk_len = 0, const double *ftrk = nullptr,
+                                                 const int ftrk_len = 0, const int ftrk_first = 0) {
   static_assert(!TRACK || (TILES == 1 && SENT != 2), "the repulsive track rides in lane 60 of the one-slot kernel");
+  static_assert(!FTRACK || (TILES == 1 && SENT != 2 && !STATICV && TRACK), "the obstacle tracks ride in lanes 0 .. M-1 of the one-slot kernel");
   extern __shared__ double smem[];
   const unsigned long long t_begin = wall_clock64();
   const int n_obs = D.n_obs;
@@ -111,6 +117,20 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
   if (TRACK && SENT == 1) {
     asm volatile("" : "+v"(trk_v));
     if (trk_len > 0) sent_p = mk(trk_v[0], trk_v[1], trk_v[2]);
+  }
+  // obstacle tracks: lane i < M takes obstacle i's position and velocity of point min(first, L-1) for step 0. The lane's
+  // pointer (its column of the [6][64] block of a point) is a global one in a VGPR pair like trk_v: six vector loads
+  // per step at immediate offsets, on vmcnt. Lanes >= M load their zero-filled columns and never use them.
+  gptr ftrk_v = (gptr)ftrk + lane;
+  const int ftrk_last = (ftrk_len > 0) ? (ftrk_len - 1) : 0;
+  const int ftrk_at = (ftrk_first < ftrk_last) ? ftrk_first : ftrk_last;   // point of step 0; step k: min(ftrk_at + k, last)
+  const lmask ftrk_m = (FTRACK && ftrk_len > 0) ? ((1ull << M) - 1ull) : 0ull;
+  if (FTRACK) {
+    asm volatile("" : "+v"(ftrk_v));
+    const gptr fp = ftrk_v + (size_t)ftrk_at * 384;
+    const bool fl = PMAF_LANE(ftrk_m);
+    O.p[0].x = fl ? fp[0] : O.p[0].x; O.p[0].y = fl ? fp[64] : O.p[0].y; O.p[0].z = fl ? fp[128] : O.p[0].z;
+    O.v[0].x = fl ? fp[192] : O.v[0].x; O.v[0].y = fl ? fp[256] : O.v[0].y; O.v[0].z = fl ? fp[320] : O.v[0].z;
   }
 
   V3 goal = mk(D.goal[pop * 3], D.goal[pop * 3 + 1], D.goal[pop * 3 + 2]);
@@ -215,6 +235,14 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
       const gptr tp = trk_v + 3 * ((n < trk_last) ? n : trk_last);
       trk_next = mk(tp[0], tp[1], tp[2]);
     }
+    // obstacle tracks: likewise -- step n's point min(ftrk_at + n, last), six loads per lane
+    V3 ftrk_np = mk(0.0, 0.0, 0.0), ftrk_nv = mk(0.0, 0.0, 0.0);
+    if (FTRACK) {
+      const int fi = (n < ftrk_last - ftrk_at) ? (ftrk_at + n) : ftrk_last;
+      const gptr fp = ftrk_v + (size_t)fi * 384;
+      ftrk_np = mk(fp[0], fp[64], fp[128]);
+      ftrk_nv = mk(fp[192], fp[256], fp[320]);
+    }
     // gate, :315-317
     // |v| < 0.5 vmax and |p - init| < 0.2 on exact squared thresholds
     // (as a lane mask built from single compares: pmaf_rollout_w64.hpp, "lane predicates as masks")
@@ -278,6 +306,11 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
     if (TRACK && SENT == 1) {   // lane 60 takes the track's point in place of o + v dt (three selects, no masked block)
       const bool tl = PMAF_LANE(trk_m);
       O.p[0].x = tl ? trk_next.x : O.p[0].x; O.p[0].y = tl ? trk_next.y : O.p[0].y; O.p[0].z = tl ? trk_next.z : O.p[0].z;
+    }
+    if (FTRACK) {   // lanes 0 .. M-1 take the point's position and velocity (six selects under a loop-invariant mask)
+      const bool fl = PMAF_LANE(ftrk_m);
+      O.p[0].x = fl ? ftrk_np.x : O.p[0].x; O.p[0].y = fl ? ftrk_np.y : O.p[0].y; O.p[0].z = fl ? ftrk_np.z : O.p[0].z;
+      O.v[0].x = fl ? ftrk_nv.x : O.v[0].x; O.v[0].y = fl ? ftrk_nv.y : O.v[0].y; O.v[0].z = fl ? ftrk_nv.z : O.v[0].z;
     }
     {
       // ONE sqrt / reciprocal / divide sequence for the whole tail: lane 63 goal distance and direction (|g|,

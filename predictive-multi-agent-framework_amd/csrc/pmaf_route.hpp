@@ -46,6 +46,9 @@ struct Input {
   // the fields the rule decides -- a handle is never moved to another kernel family for its track --; Route::carries_track
   // says whether the launch the route names has the variant that follows one (pmaf_k_track.hip)
   bool tracked = false;
+  // obstacle tracks are attached (include/pmaf.h "obstacle tracks"): likewise an input that moves no field the rule
+  // decides; Route::carries_field_tracks says whether the routed launch exists as k_rollout_w64_ftrack (pmaf_k_ftrack.hip)
+  bool field_tracked = false;
 };
 
 struct Route {
@@ -64,6 +67,7 @@ struct Route {
   int n_blocks = 1;             // blocks per population of the GROUP / GENERIC grid (and of k_plan_steps)
   size_t lds_rollout = 0;       // dynamic LDS of the one-wave rollout launch (and of k_plan_steps), bytes
   bool carries_track = false;   // the routed launch exists as k_rollout_w64_track (whatever Input::tracked says)
+  bool carries_field_tracks = false;   // ... and as k_rollout_w64_ftrack (whatever Input::field_tracked says)
 };
 
 static inline const char *family_name(Family f) {
@@ -194,6 +198,8 @@ static inline Route route(const Input &in) {
   // ---- the repulsive track: k_rollout_w64_track is the one-slot wave-per-agent kernel (both ordered sums, PLAIN and
   // general step) of the default arithmetic policy, without the priority-slicing loop
   r.carries_track = r.family == WAVE_PER_AGENT && r.slots == 1 && r.tiles == 1 && in.math == pmaf::MATH_XACT && !r.sliced;
+  // ---- the obstacle tracks: k_rollout_w64_ftrack is the same kernel with the tracked field obstacles
+  r.carries_field_tracks = r.carries_track;
   return r;
 }
 

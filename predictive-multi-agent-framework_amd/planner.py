@@ -81,6 +81,9 @@ SYMBOLS = {
     "pmaf_set_repulsive_track": (C.c_int, [_V, _dp, _ip, C.c_int32]),
     "pmaf_couple_tracks": (C.c_int, [_V, _ip, C.c_int32]),
     "pmaf_get_repulsive_track": (C.c_int, [_V, _dp, _ip, C.c_int32]),
+    "pmaf_set_obstacle_tracks": (C.c_int, [_V, _dp, _ip, C.c_int32]),
+    "pmaf_set_obstacle_track_offset": (C.c_int, [_V, _ip]),
+    "pmaf_get_obstacle_tracks": (C.c_int, [_V, _dp, _ip, _ip, C.c_int32]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -793,6 +796,44 @@ class PmafPlanner:
         buf = np.zeros((self.P, m, 3))
         self._chk(self.L.pmaf_get_repulsive_track(self._h, _p(buf), _pi(ln), m))
         return [buf[p, :ln[p]].copy() for p in range(self.P)]
+
+    # -- obstacle tracks (include/pmaf.h "obstacle tracks") --
+    def set_obstacle_tracks(self, tracks, lengths=None):
+        """tracks: None (detach), one [L][M][6] array (single population), or a sequence of P entries, each [L_p][M][6] or
+        None; or -- with lengths [P] -- a padded [P][max_len][M][6] array handed over as it is. Every offset becomes 0."""
+        M = self.n_obs - 1
+        if tracks is None:
+            self._chk(self.L.pmaf_set_obstacle_tracks(self._h, None, None, 0))
+            return
+        if lengths is not None:
+            buf = _d(tracks).reshape(self.P, -1, M, 6)
+            ln = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, dtype=np.int32), (self.P,)))
+        else:
+            if self.P == 1 and not isinstance(tracks, (list, tuple)):
+                tracks = [tracks]
+            assert len(tracks) == self.P
+            tr = [np.zeros((0, M, 6)) if t is None else _d(t).reshape(-1, M, 6) for t in tracks]
+            ln = np.array([len(t) for t in tr], dtype=np.int32)
+            buf = np.zeros((self.P, max(1, int(ln.max())), M, 6))
+            for p, t in enumerate(tr):
+                buf[p, :len(t)] = t
+        self._chk(self.L.pmaf_set_obstacle_tracks(self._h, _p(buf), _pi(ln), int(buf.shape[1])))
+
+    def set_obstacle_track_offset(self, first):
+        """first: [P] (or one number for all): the point of the tracks prediction step 0 reads"""
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(first, dtype=np.int32), (self.P,)))
+        self._chk(self.L.pmaf_set_obstacle_track_offset(self._h, _pi(f)))
+
+    def get_obstacle_tracks(self):
+        """what the last launched rollout used: (a list of P arrays [L_p][M][6] (L_p == 0: none), the offsets [P])"""
+        M = self.n_obs - 1
+        ln = np.zeros(self.P, dtype=np.int32)
+        first = np.zeros(self.P, dtype=np.int32)
+        self._chk(self.L.pmaf_get_obstacle_tracks(self._h, None, _pi(ln), _pi(first), 0))
+        m = max(1, int(ln.max()))
+        buf = np.zeros((self.P, m, M, 6))
+        self._chk(self.L.pmaf_get_obstacle_tracks(self._h, _p(buf), _pi(ln), _pi(first), m))
+        return [buf[p, :ln[p]].copy() for p in range(self.P)], first
 
     def launch_config(self):
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)

@@ -39,6 +39,11 @@ UNITS = [
       "C3 k_rollout_w64<2,3,dpp,plain>": "_Z13k_rollout_w64ILi2ELi3ELb1ELb1EEv7DevView10CostParams"}),
     ("c5_contracted", "pmaf_k_grp.hip", ["-DPMAF_GRP_MATH=3", "-ffp-contract=fast"],
      {"C5 k_rollout_grp<16,2,3>": "_Z13k_rollout_grpILi16ELi2ELi3EEv7DevView10CostParams"}),
+    # the tracked variants of the one-slot kernel (the flags of c1c2_strict: the same body)
+    ("track_strict", "pmaf_k_track.hip", ["-DPMAF_W64_MATH=2", "-falign-loops=32", "-DPMAF_SUM_TAIL_PIN=1"],
+     {"repulsive track k_rollout_w64_track<dpp,plain>": "_Z19k_rollout_w64_trackILb1ELb1EEv7DevView10CostParams9TrackArgs"}),
+    ("ftrack_strict", "pmaf_k_ftrack.hip", ["-DPMAF_W64_MATH=2", "-falign-loops=32", "-DPMAF_SUM_TAIL_PIN=1"],
+     {"obstacle tracks k_rollout_w64_ftrack<dpp,plain>": "_Z20k_rollout_w64_ftrackILb1ELb1EEv7DevView10CostParams9TrackArgs10FTrackArgs"}),
 ]
 
 
