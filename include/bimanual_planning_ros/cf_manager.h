@@ -486,18 +486,16 @@ class CfManager {
   // ... and of every predicted agent's path, with the step and obstacle of the closest approach and the first step whose
   // clearance falls below `margin` (pmaf_evaluate_paths; no reference equivalent)
   PathAudit evaluatePaths(const std::vector<Obstacle> &obstacles, const double margin = 0.0) {
-    require();
-    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("evaluatePaths: obstacle count changed");
-    const std::vector<double> obs = flat(obstacles);
-    PathAudit r;
-    r.clearance.resize(n_agents_);
-    std::vector<int32_t> st(n_agents_), ob(n_agents_), fv(n_agents_);
-    check(pmaf_evaluate_paths(h_, obs.data(), margin, r.clearance.data(), st.data(), ob.data(), fv.data(), nullptr),
-          "evaluatePaths");
-    r.step.assign(st.begin(), st.end());
-    r.obstacle.assign(ob.begin(), ob.end());
-    r.first_violation.assign(fv.begin(), fv.end());
-    return r;
+    return evaluatePathsImpl(obstacles, margin, false, nullptr, "evaluatePaths");
+  }
+  // ... with the field obstacles where the rollouts saw them: on the obstacle tracks (setObstacleTracks), read from the
+  // offset `first` -- one entry, or empty for the offset the tracks are at (pmaf_evaluate_paths_tracked, include/pmaf.h
+  // "audits against the obstacle tracks"). The trailing obstacle and the radii stay the list's; without tracks this is
+  // evaluatePaths. std::out_of_range for a negative offset or more than one, std::runtime_error for an offset without tracks.
+  PathAudit evaluatePathsTracked(const std::vector<Obstacle> &obstacles, const double margin = 0.0,
+                                 const std::vector<int> &first = {}) {
+    const int32_t f = trackedFirst(first, "evaluatePathsTracked");
+    return evaluatePathsImpl(obstacles, margin, true, first.empty() ? nullptr : &f, "evaluatePathsTracked");
   }
   // The other arm of a bimanual node is a second CfManager: every predicted path of THIS manager against every path of
   // `other_paths` (the other manager's getPredictedPaths(), or its selected path alone), both on the same step grid, an
@@ -516,6 +514,30 @@ class CfManager {
   }
 
  private:
+  // one body behind evaluatePaths and evaluatePathsTracked (first: the offset or NULL)
+  PathAudit evaluatePathsImpl(const std::vector<Obstacle> &obstacles, const double margin, const bool tracked,
+                              const int32_t *first, const char *who) {
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range(std::string(who) + ": obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    PathAudit r;
+    r.clearance.resize(n_agents_);
+    std::vector<int32_t> st(n_agents_), ob(n_agents_), fv(n_agents_);
+    check(tracked ? pmaf_evaluate_paths_tracked(h_, obs.data(), first, margin, r.clearance.data(), st.data(), ob.data(),
+                                                fv.data(), nullptr)
+                  : pmaf_evaluate_paths(h_, obs.data(), margin, r.clearance.data(), st.data(), ob.data(), fv.data(), nullptr),
+          who);
+    r.step.assign(st.begin(), st.end());
+    r.obstacle.assign(ob.begin(), ob.end());
+    r.first_violation.assign(fv.begin(), fv.end());
+    return r;
+  }
+  // the optional offset of the tracked audits: none, or the one population's
+  static int32_t trackedFirst(const std::vector<int> &first, const char *who) {
+    if (first.size() > 1) throw std::out_of_range(std::string(who) + ": one offset per population (this manager has one)");
+    if (!first.empty() && first[0] < 0) throw std::out_of_range(std::string(who) + ": the offset must be >= 0");
+    return first.empty() ? 0 : (int32_t)first[0];
+  }
   // the other arm's paths as the track calls take them: [n][max_prediction_steps][3] and the point counts
   void packTracks(const std::vector<std::vector<Vector3d>> &other_paths, std::vector<double> &tracks, std::vector<int32_t> &len,
                   const char *who) const {
@@ -590,19 +612,43 @@ class CfManager {
   // (agent_id selects the gains only). Call after evaluateAgents.
   ClearSelection selectClear(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
                              const bool adopt = true) {
+    return selectClearImpl(obstacles, margin, horizon, adopt, false, nullptr, false, "selectClear");
+  }
+  // ... with the field obstacles where the rollouts saw them: on the obstacle tracks (setObstacleTracks), read from the
+  // offset `first` -- one entry, or empty for the offset the tracks are at (pmaf_select_clear_tracked, include/pmaf.h
+  // "audits against the obstacle tracks"). The trailing obstacle stays on the list's line, or is left out with
+  // skip_trailing; the radii stay the list's; pick, hysteresis and adopt as selectClear; without tracks this is
+  // selectClear. std::out_of_range for a negative offset or more than one, std::runtime_error for an offset without tracks.
+  ClearSelection selectClearTracked(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                    const bool adopt = true, const std::vector<int> &first = {},
+                                    const bool skip_trailing = false) {
+    const int32_t f = trackedFirst(first, "selectClearTracked");
+    return selectClearImpl(obstacles, margin, horizon, adopt, true, first.empty() ? nullptr : &f, skip_trailing,
+                           "selectClearTracked");
+  }
+
+ private:
+  // one body behind selectClear and selectClearTracked (first: the offset or NULL)
+  ClearSelection selectClearImpl(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                 const bool adopt, const bool tracked, const int32_t *first, const bool skip_trailing,
+                                 const char *who) {
     require();
-    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("selectClear: obstacle count changed");
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range(std::string(who) + ": obstacle count changed");
     const std::vector<double> obs = flat(obstacles);
     const int32_t prev = prev_pick_;
     int32_t pick = -1, rule = -1, n_clear = 0, fv = 0;
     ClearSelection r;
-    check(pmaf_select_clear(h_, obs.data(), margin, horizon, &prev, adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost,
-                            &r.clearance, &fv),
-          "selectClear");
+    check(tracked ? pmaf_select_clear_tracked(h_, obs.data(), first, margin, horizon, skip_trailing ? 1 : 0, &prev,
+                                              adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost, &r.clearance, &fv)
+                  : pmaf_select_clear(h_, obs.data(), margin, horizon, &prev, adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost,
+                                      &r.clearance, &fv),
+          who);
     r.pick = pick; r.rule = rule; r.n_clear = n_clear; r.first_violation = fv;
     prev_pick_ = pick;
     return r;
   }
+
+ public:
   // The joint pick of one arm per CfManager: the cheapest agent whose first `horizon` path points keep `margin` to the list
   // as it is NOW -- its trailing obstacle, the sphere at the other arm's last set-point, left out -- AND `pair_margin` to
   // one of `other_paths` (the other manager's getSelectedPath(), or several candidates), both on the same step grid
@@ -661,14 +707,16 @@ class CfManager {
   }
   // planCallback's sequence with the selection held against the live list: stopPrediction, evaluateAgents,
   // selectClear(adopt), moveRealEEAgent(agent_id = pick), resetEEAgents to the new set-point, startPrediction. Returns
-  // the pick.
+  // the pick. tracked: the selection is selectClearTracked -- against the obstacle tracks the rollouts followed, at the
+  // offset they are at (advanceObstacleTracks between two ticks moves both on).
   int planTickAudited(const std::vector<Obstacle> &obstacles, const double delta_t, const double k_goal_dist,
                       const double k_path_len, const double k_safe_dist, const double k_workspace,
                       const Vector6d des_ws_limits, const double margin, const int horizon,
-                      Vector3d *next_position = nullptr, ClearSelection *sel = nullptr) {
+                      Vector3d *next_position = nullptr, ClearSelection *sel = nullptr, const bool tracked = false) {
     stopPrediction();
     evaluateAgents(obstacles, k_goal_dist, k_path_len, k_safe_dist, k_workspace, des_ws_limits);
-    const ClearSelection s = selectClear(obstacles, margin, horizon, true);
+    const ClearSelection s = tracked ? selectClearTracked(obstacles, margin, horizon, true)
+                                     : selectClear(obstacles, margin, horizon, true);
     moveRealEEAgent(obstacles, delta_t, 1, s.pick);
     double p[3], v[3];
     check(pmaf_get_real_state(h_, p, v, nullptr), "planTickAudited");

@@ -574,8 +574,10 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  * pmaf_tick when the route became unsupported after the attach. A handle with only a repulsive track, and every
  * handle without tracks, launches what it launched before these calls existed.
  * Limits: no tracks on the multi-slot (> 60 field obstacles), multi-wave, group, sliced and generic routes, nor under
- * the other arithmetic policies; the audits and the selections keep the live list's straight lines -- they do not see
- * the tracks; the tracks come from the host only (no device-side source like pmaf_couple_tracks); the planner node
+ * the other arithmetic policies; pmaf_evaluate_paths_tracked and pmaf_select_clear_tracked (below) audit and select
+ * against the tracks, every other audit and selection -- pmaf_evaluate_paths, pmaf_evaluate_path, pmaf_select_clear,
+ * the cross audits, the joint selections pmaf_select_pair_clear / pmaf_select_clear_tracks -- keeps the live list's
+ * straight lines and does not see them; the tracks come from the host only (no device-side source like pmaf_couple_tracks); the planner node
  * (planner_node.h) does not use them.
  * pmaf_set_obstacle_tracks: tracks [P][max_len][M][6] (M = n_obstacles - 1; x y z vx vy vz), len [P]; takes effect from
  *   the next pmaf_start / pmaf_tick and stays until replaced; every population's offset becomes 0. tracks == NULL,
@@ -591,6 +593,48 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
 int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len);
 int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first);
 int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len);
+
+/* ---- audits against the obstacle tracks: the path audit and the clear selection where the rollouts saw the field
+ * obstacles (exports added under ABI 7) ----
+ * On a handle with obstacle tracks the rollout bends its paths round the predicted positions, while pmaf_evaluate_paths
+ * and pmaf_select_clear hold every path against the list's straight lines: a path bent round a predicted turn is
+ * rejected where the line cuts through it, and a path through the place the obstacle turns into is selected as clear.
+ * These two calls are exactly pmaf_evaluate_paths' and pmaf_select_clear's contracts with ONE change, the position of a
+ * tracked field obstacle. For population p let L = len[p] be the length of the tracks attached NOW -- what the next
+ * rollout launch would follow; the setters synchronise, so there is one set of tracks --, f = first[p] when first is
+ * given, else the handle's current offset of p, and M = n_obstacles - 1.
+ *   tracked field obstacle (L > 0, j < M):  o_j^k = the POSITION of track point min(f + k, L-1), taken verbatim and held
+ *              at the end -- the rollout's rule: step k from x_k sees point min(first + k, L-1). The track's velocities
+ *              are not read. f may be as large as INT32_MAX: min(f + k, L-1) = min(min(f, L-1) + k, L-1), and the
+ *              right-hand side is what is computed.
+ *   trailing obstacle (j = M):              stays on the list's iterated line o^{k+1} = o^k + RN(v dt), as in the
+ *              untracked calls (it does not follow a repulsive track either). pmaf_evaluate_paths_tracked always
+ *              includes it; pmaf_select_clear_tracked leaves it out when skip_trailing != 0 (the joint selection's
+ *              convention: obstacles 0 .. n_obstacles - 2 of every list are audited).
+ *   untracked population (L == 0):          every obstacle is on the list's line: the result is bit for bit that of
+ *              the untracked call.
+ *   radii:     radius + r_j with r_j from the CALLER'S list, as in the untracked audits -- NOT the creation list's radii
+ *              the rollout uses.
+ * Unchanged: the window w = min(n, horizon), the strict `<` from +infinity, the tie rules (smallest k, then smallest j,
+ * across tracked and trailing obstacles alike), first_violation, per_obstacle, the rules 0 / 1 / 2 with the 0.9
+ * hysteresis, the outputs and which of them may be NULL. adopt works like pmaf_adopt_best. The calls wait for a running
+ * rollout, refuse a handle whose tick was abandoned (pmaf_select_clear_tracked; PMAF_ERR_STATE until pmaf_stop), and
+ * with adopt == 0 change no planner state: neither the attached tracks nor the handle's offsets move, and a tick
+ * sequence with such calls in between is bit-identical to one without.
+ * first [P] or NULL. An entry below 0: PMAF_ERR_INVALID. first != NULL on a handle with no tracks attached:
+ * PMAF_ERR_STATE, like pmaf_set_obstacle_track_offset. first == NULL on a handle without tracks is allowed and gives the
+ * untracked result. Everything else is validated as in the untracked calls.
+ * Tracks whose points are the iterated straight lines of the caller's list give bit for bit the untracked results.
+ * Intended six-call tick on a tracked handle (CfManager::planTickAudited(..., tracked = true)):
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_clear_tracked(adopt = 1) -> pmaf_move_real(agent_id = pick)
+ *   -> pmaf_reset_agents -> [pmaf_set_obstacle_track_offset] -> pmaf_start */
+int pmaf_evaluate_paths_tracked(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin,
+                                double *clearance, int32_t *step, int32_t *obstacle, int32_t *first_violation,
+                                double *per_obstacle);
+int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin,
+                              int32_t horizon, int32_t skip_trailing, const int32_t *prev_idx, int32_t adopt,
+                              int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
+                              int32_t *first_violation);
 
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last

@@ -2,6 +2,7 @@
 // obstacle distance, the path audit, the selection against the live list (pmaf_select_clear / pmaf_adopt_best), the six
 // cross-audit calls, the joint selection, the link force. None of it runs inside pmaf_tick.
 #include "pmaf_host_impl.hpp"
+#include "pmaf_auditft.hpp"
 
 extern "C" {
 
@@ -21,10 +22,21 @@ int pmaf_eval_obstacle_distance(pmaf_planner *h, const double *obstacles, double
 // The reference declares CfManager::evaluatePath(const std::vector<Obstacle> &) (B/include/bimanual_planning_ros/
 // cf_manager.h:130) without defining it, and evaluateAgents ignores its obstacle list (B/src/cf_manager.cpp:293-356).
 // One implementation behind both exports: only_best = the selected agent of every population (outputs [P]).
+// tracked (pmaf_evaluate_paths_tracked): the field obstacles of a population with tracks on the handle's resident
+// tracks, read from `first` (NULL: the handle's offsets); the track buffer is then built by k_audit_track_ft.
+struct TrackedCall {
+  const int32_t *first;   // [P] or NULL
+  const char *who;
+};
+static void check_tracked_first(const pmaf_planner *h, const TrackedCall &T);
+static FTrackArgs tracked_args(pmaf_planner *h, const TrackedCall &T);
+
 static void evaluate_paths(pmaf_planner *h, const double *obstacles, double margin, bool only_best, double *clearance,
-                           int32_t *step, int32_t *obstacle, int32_t *first_violation, double *per_obstacle) {
+                           int32_t *step, int32_t *obstacle, int32_t *first_violation, double *per_obstacle,
+                           const TrackedCall *tracked = nullptr) {
   const DevView &D = h->D;
   const size_t n_obs = (size_t)D.n_obs, rows = only_best ? (size_t)D.P : (size_t)D.P * D.N;
+  if (tracked) check_tracked_first(h, *tracked);
   check_range(obstacles, (size_t)D.P * n_obs * 7, "obstacles");
   check_range(&margin, 1, "margin");
   if ((size_t)D.cap * n_obs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "path audit: max_prediction_steps * n_obstacles must stay below 2^31");
@@ -49,7 +61,12 @@ static void evaluate_paths(pmaf_planner *h, const double *obstacles, double marg
   A.step = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
   A.obstacle = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
   A.first_violation = reinterpret_cast<int32_t *>(d_out + off); off += sizeof(int32_t) * rows;
-  pmaf_k_launch_path_audit(D, A, reinterpret_cast<double *>(h->d_audit.get()), h->stream);
+  if (tracked && h->ftrk.on()) {   // (no tracks attached: the untracked launch, whose result it is)
+    pmaf_k_launch_audit_track_ft(D, A.obs, tracked_args(h, *tracked), reinterpret_cast<double *>(h->d_audit.get()), h->stream);
+    pmaf_k_launch_path_audit_only(D, A, h->stream);
+  } else {
+    pmaf_k_launch_path_audit(D, A, reinterpret_cast<double *>(h->d_audit.get()), h->stream);
+  }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(h->h_audit.get(), d_out, off, hipMemcpyDeviceToHost, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -68,6 +85,16 @@ int pmaf_evaluate_paths(pmaf_planner *h, const double *obstacles, double margin,
   return guarded([&] {
     REQUIRE(h && obstacles && clearance, "pmaf_evaluate_paths: NULL argument");
     evaluate_paths(h, obstacles, margin, false, clearance, step, obstacle, first_violation, per_obstacle);
+  });
+}
+
+int pmaf_evaluate_paths_tracked(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin,
+                                double *clearance, int32_t *step, int32_t *obstacle, int32_t *first_violation,
+                                double *per_obstacle) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_evaluate_paths_tracked: NULL argument");
+    const TrackedCall T{first, "pmaf_evaluate_paths_tracked"};
+    evaluate_paths(h, obstacles, margin, false, clearance, step, obstacle, first_violation, per_obstacle, &T);
   });
 }
 
@@ -94,6 +121,9 @@ static size_t select_pairclear_rec(const DevView &D) {
   return (size_t)D.P * 7 * D.n_obs + (size_t)D.P * PMAF_SELECT_REC + ((size_t)D.P + 1) / 2;
 }
 
+// ... and of the tracked calls' offsets behind it
+static size_t select_tracked_first(const DevView &D) { return select_pairclear_rec(D) + PMAF_PAIRCLEAR_REC; }
+
 static void select_scratch(pmaf_planner *h) {
   if (h->sel.host()) return;
   const DevView &D = h->D;
@@ -102,8 +132,32 @@ static void select_scratch(pmaf_planner *h) {
   h->d_sel_clr = h->dalloc_untracked<double>(PN);
   h->d_sel_fv = h->dalloc_untracked<int32_t>(PN);
   h->d_adopt_idx = h->dalloc_untracked<int32_t>((size_t)D.P);
-  // list | result records [P] | previous picks [P] (int32, padded to a double) | the joint selection's record
-  h->sel.alloc(sizeof(double) * (select_pairclear_rec(D) + PMAF_PAIRCLEAR_REC));
+  // list | result records [P] | previous picks [P] (int32, padded to a double) | the joint selection's record | the
+  // tracked calls' offsets [P] (int32, padded)
+  h->sel.alloc(sizeof(double) * (select_tracked_first(D) + ((size_t)D.P + 1) / 2));
+}
+
+// ---- the audits against the obstacle tracks (include/pmaf.h "audits against the obstacle tracks"): what the tracked
+// calls add to the untracked ones' bodies; kernels in pmaf_k_auditft.hip ----
+static void check_tracked_first(const pmaf_planner *h, const TrackedCall &T) {
+  if (!T.first) return;
+  for (int p = 0; p < h->D.P; p++) REQUIRE(T.first[p] >= 0, std::string(T.who) + ": first must be >= 0");
+  if (!h->ftrk.on()) fail(PMAF_ERR_STATE, std::string(T.who) + ": no obstacle tracks are attached (pmaf_set_obstacle_tracks)");
+}
+
+// the handle's resident tracks as the kernels read them; the call's offsets travel like prev_idx, in mapped pinned
+// memory (the caller has waited for the stream: no earlier call's kernel still reads the slot)
+static FTrackArgs tracked_args(pmaf_planner *h, const TrackedCall &T) {
+  const pmaf_planner::FieldTrack &f = h->ftrk;
+  if (h->D.n_obs > PMAF_FTRACK_LANES) fail(PMAF_ERR_STATE, std::string(T.who) + ": obstacle tracks on a handle of more than 64 obstacles");
+  FTrackArgs F{f.d_pts.get(), f.d_len.get(), f.d_first.get(), f.stride};
+  if (T.first) {
+    select_scratch(h);
+    const size_t at = select_tracked_first(h->D);
+    std::memcpy(h->sel.host() + at, T.first, sizeof(int32_t) * (size_t)h->D.P);
+    F.first = reinterpret_cast<const int32_t *>(h->sel.dev() + at);
+  }
+  return F;
 }
 
 // Spin until a selection kernel has published `seq` in the last entry of each of `count` records of `rec_doubles`
@@ -122,51 +176,78 @@ static void wait_select(pmaf_planner *h, const double *rec, int count, size_t re
       who, ": the selection kernel finished without publishing its result");
 }
 
+// One body behind pmaf_select_clear and pmaf_select_clear_tracked (tracked != NULL; n_audit = n_obs, or n_obs - 1 when
+// the tracked call skips the trailing obstacle). Called inside guarded().
+static void select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
+                         int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
+                         int32_t *first_violation, const std::string &who, const TrackedCall *tracked, bool skip_trailing) {
+  REQUIRE(h && obstacles && pick, who + ": NULL argument");
+  const DevView &D = h->D;
+  REQUIRE(horizon >= 1, who + ": horizon must be >= 1");
+  if (prev_idx)
+    for (int p = 0; p < D.P; p++) REQUIRE(prev_idx[p] >= -1 && prev_idx[p] < D.N, who + ": prev_idx out of range");
+  if (tracked) check_tracked_first(h, *tracked);
+  check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+  check_range(&margin, 1, "margin");
+  h->use_device();
+  require_drained(h, who.c_str());
+  sync(h);   // behind the running rollout, like the getters of its results
+  select_scratch(h);
+  const size_t list = (size_t)D.P * 7 * D.n_obs;
+  double *rec = h->sel.host() + list;
+  int32_t *prev_h = reinterpret_cast<int32_t *>(rec + (size_t)D.P * PMAF_SELECT_REC);
+  aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
+  if (prev_idx) std::memcpy(prev_h, prev_idx, sizeof(int32_t) * (size_t)D.P);
+  SelectArgs A{};
+  A.obs_src = h->sel.dev();
+  A.obs = h->d_sel_obs;
+  A.margin = margin;
+  A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
+  A.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;   // (pmaf_select_clear: every obstacle counts, the trailing one included)
+  A.adopt = adopt ? 1 : 0;
+  A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->sel.dev() + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
+  A.clr = h->d_sel_clr;
+  A.fv = h->d_sel_fv;
+  A.result = h->sel.dev() + list;
+  A.seq = (h->sel_seq += 1.0);
+  if (tracked && h->ftrk.on()) {   // (no tracks attached: the untracked audit, whose result it is)
+    const FTrackArgs F = tracked_args(h, *tracked);
+    pmaf_k_launch_select_stage(D, A, h->stream);
+    pmaf_k_launch_select_audit_ft(D, A, F, h->stream);
+    pmaf_k_launch_select_pick(D, A, h->stream);
+  } else {
+    pmaf_k_launch_select_clear(D, A, h->stream);
+  }
+  HIP_CHECK(hipGetLastError());
+  wait_select(h, rec, D.P, PMAF_SELECT_REC, A.seq, who.c_str());
+  if (adopt) h->has_best_h = 1;
+  for (int p = 0; p < D.P; p++) {
+    const double *r = rec + (size_t)p * PMAF_SELECT_REC;
+    pick[p] = (int32_t)r[0];
+    if (rule) rule[p] = (int32_t)r[1];
+    if (n_clear) n_clear[p] = (int32_t)r[2];
+    if (first_violation) first_violation[p] = (int32_t)r[3];
+    if (cost) cost[p] = r[4];
+    if (clearance) clearance[p] = r[5];
+  }
+}
+
 int pmaf_select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
                       int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
                       int32_t *first_violation) {
   return guarded([&] {
-    REQUIRE(h && obstacles && pick, "pmaf_select_clear: NULL argument");
-    const DevView &D = h->D;
-    REQUIRE(horizon >= 1, "pmaf_select_clear: horizon must be >= 1");
-    if (prev_idx)
-      for (int p = 0; p < D.P; p++) REQUIRE(prev_idx[p] >= -1 && prev_idx[p] < D.N, "pmaf_select_clear: prev_idx out of range");
-    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
-    check_range(&margin, 1, "margin");
-    h->use_device();
-    require_drained(h, "pmaf_select_clear");
-    sync(h);   // behind the running rollout, like the getters of its results
-    select_scratch(h);
-    const size_t list = (size_t)D.P * 7 * D.n_obs;
-    double *rec = h->sel.host() + list;
-    int32_t *prev_h = reinterpret_cast<int32_t *>(rec + (size_t)D.P * PMAF_SELECT_REC);
-    aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
-    if (prev_idx) std::memcpy(prev_h, prev_idx, sizeof(int32_t) * (size_t)D.P);
-    SelectArgs A{};
-    A.obs_src = h->sel.dev();
-    A.obs = h->d_sel_obs;
-    A.margin = margin;
-    A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
-    A.n_audit = D.n_obs;                             // every obstacle counts, the trailing one included
-    A.adopt = adopt ? 1 : 0;
-    A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->sel.dev() + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
-    A.clr = h->d_sel_clr;
-    A.fv = h->d_sel_fv;
-    A.result = h->sel.dev() + list;
-    A.seq = (h->sel_seq += 1.0);
-    pmaf_k_launch_select_clear(D, A, h->stream);
-    HIP_CHECK(hipGetLastError());
-    wait_select(h, rec, D.P, PMAF_SELECT_REC, A.seq, "pmaf_select_clear");
-    if (adopt) h->has_best_h = 1;
-    for (int p = 0; p < D.P; p++) {
-      const double *r = rec + (size_t)p * PMAF_SELECT_REC;
-      pick[p] = (int32_t)r[0];
-      if (rule) rule[p] = (int32_t)r[1];
-      if (n_clear) n_clear[p] = (int32_t)r[2];
-      if (first_violation) first_violation[p] = (int32_t)r[3];
-      if (cost) cost[p] = r[4];
-      if (clearance) clearance[p] = r[5];
-    }
+    select_clear(h, obstacles, margin, horizon, prev_idx, adopt, pick, rule, n_clear, cost, clearance, first_violation,
+                 "pmaf_select_clear", nullptr, false);
+  });
+}
+
+int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin, int32_t horizon,
+                              int32_t skip_trailing, const int32_t *prev_idx, int32_t adopt, int32_t *pick, int32_t *rule,
+                              int32_t *n_clear, double *cost, double *clearance, int32_t *first_violation) {
+  return guarded([&] {
+    const TrackedCall T{first, "pmaf_select_clear_tracked"};
+    select_clear(h, obstacles, margin, horizon, prev_idx, adopt, pick, rule, n_clear, cost, clearance, first_violation,
+                 T.who, &T, skip_trailing != 0);
   });
 }
 

@@ -972,6 +972,11 @@ void pmaf_k_launch_path_audit(const DevView &D, const AuditArgs &A, double *trac
   hipLaunchKernelGGL(k_path_audit, dim3((unsigned)(A.only_best ? 1 : D.N), (unsigned)D.P), dim3(64 * PMAF_AUDIT_WAVES), 0, s, D, A);
 }
 
+// k_path_audit alone (pmaf_auditft.hpp): the tracked audit builds A.track itself
+void pmaf_k_launch_path_audit_only(const DevView &D, const AuditArgs &A, hipStream_t s) {
+  hipLaunchKernelGGL(k_path_audit, dim3((unsigned)(A.only_best ? 1 : D.N), (unsigned)D.P), dim3(64 * PMAF_AUDIT_WAVES), 0, s, D, A);
+}
+
 void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s) {
   const dim3 grid((unsigned)((A.n_b + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE), (unsigned)((A.n_a + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE));
   hipLaunchKernelGGL(k_cross_audit, grid, dim3(PMAF_XAUDIT_THREADS), 0, s, A);

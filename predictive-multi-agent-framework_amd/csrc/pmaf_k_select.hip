@@ -213,6 +213,16 @@ void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream
   hipLaunchKernelGGL(k_select_pick, dim3((unsigned)D.P), dim3(64), 0, s, D, A);
 }
 
+// the first and the last of the three alone (pmaf_auditft.hpp): the tracked selection puts its own audit between them
+void pmaf_k_launch_select_stage(const DevView &D, const SelectArgs &A, hipStream_t s) {
+  const int total = D.P * 7 * D.n_obs;
+  hipLaunchKernelGGL(k_select_stage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, A.obs_src, A.obs);
+}
+
+void pmaf_k_launch_select_pick(const DevView &D, const SelectArgs &A, hipStream_t s) {
+  hipLaunchKernelGGL(k_select_pick, dim3((unsigned)D.P), dim3(64), 0, s, D, A);
+}
+
 void pmaf_k_launch_adopt_best(const DevView &D, const AdoptArgs &A, hipStream_t s) {
   hipLaunchKernelGGL(k_adopt_best, dim3((unsigned)D.P), dim3(64), 0, s, D, A);
 }

@@ -84,6 +84,9 @@ SYMBOLS = {
     "pmaf_set_obstacle_tracks": (C.c_int, [_V, _dp, _ip, C.c_int32]),
     "pmaf_set_obstacle_track_offset": (C.c_int, [_V, _ip]),
     "pmaf_get_obstacle_tracks": (C.c_int, [_V, _dp, _ip, _ip, C.c_int32]),
+    "pmaf_evaluate_paths_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, _dp, _ip, _ip, _ip, _dp]),
+    "pmaf_select_clear_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp,
+                                            _dp, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -499,12 +502,16 @@ class PmafPlanner:
                                                   float(pair_margin), _pi(lt), _pi(pv), 1 if adopt else 0, *args))
         return self._joint_dict(o)
 
-    def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None):
+    def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None, tracked=False):
         """the six-call tick: stop, evaluate, select_clear(adopt), move_real(agent_id = pick), reset_agents to the new
-        set-point, start. Returns select_clear's dict, with `best` = evaluate's own selection"""
+        set-point, start. Returns select_clear's dict, with `best` = evaluate's own selection. tracked=True selects with
+        select_clear_tracked: against the attached obstacle tracks at the handle's offsets"""
         self.stop()
         best = self.evaluate(cost_gains, ws)
-        sel = self.select_clear(obstacles, margin, horizon, prev=prev, adopt=True)
+        if tracked:
+            sel = self.select_clear_tracked(obstacles, margin, horizon, prev=prev, adopt=True)
+        else:
+            sel = self.select_clear(obstacles, margin, horizon, prev=prev, adopt=True)
         self.move_real(obstacles, dt, 1, sel["pick"])
         pos, vel, _ = self.real_state()
         self.last_next_pos, self.last_next_vel = np.array(pos, copy=True), np.array(vel, copy=True)
@@ -834,6 +841,39 @@ class PmafPlanner:
         buf = np.zeros((self.P, m, M, 6))
         self._chk(self.L.pmaf_get_obstacle_tracks(self._h, _p(buf), _pi(ln), _pi(first), m))
         return [buf[p, :ln[p]].copy() for p in range(self.P)], first
+
+    # -- audits against the obstacle tracks (include/pmaf.h "audits against the obstacle tracks") --
+    def _first(self, first):
+        return None if first is None else np.ascontiguousarray(np.broadcast_to(np.asarray(first, dtype=np.int32), (self.P,)))
+
+    def evaluate_paths_tracked(self, obstacles, margin=0.0, per_obstacle=False, first=None):
+        """evaluate_paths with the field obstacles of a tracked population on the attached obstacle tracks, read from
+        `first` ([P], one number for all, or None: the handle's offsets) (pmaf_evaluate_paths_tracked): the same dict"""
+        o = self._obs(obstacles)
+        out = {"clearance": np.zeros((self.P, self.N))}
+        for k in ("step", "obstacle", "first_violation"):
+            out[k] = np.zeros((self.P, self.N), dtype=np.int32)
+        po = np.zeros((self.P, self.N, self.n_obs)) if per_obstacle else None
+        self._chk(self.L.pmaf_evaluate_paths_tracked(self._h, _p(o), _pi(self._first(first)), float(margin),
+                                                     _p(out["clearance"]), _pi(out["step"]), _pi(out["obstacle"]),
+                                                     _pi(out["first_violation"]), _p(po)))
+        if per_obstacle:
+            out["per_obstacle"] = po
+        return {k: self._sq(v) for k, v in out.items()}
+
+    def select_clear_tracked(self, obstacles, margin, horizon, prev=None, adopt=False, first=None, skip_trailing=False):
+        """select_clear with the field obstacles of a tracked population on the attached obstacle tracks, read from
+        `first` ([P], one number for all, or None: the handle's offsets); skip_trailing leaves the lists' last obstacle
+        out (pmaf_select_clear_tracked): the same dict"""
+        o = self._obs(obstacles)
+        pv = None if prev is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prev, dtype=np.int32), (self.P,)))
+        out = {k: np.zeros(self.P, dtype=np.int32) for k in ("pick", "rule", "n_clear", "first_violation")}
+        out["cost"], out["clearance"] = np.zeros(self.P), np.zeros(self.P)
+        self._chk(self.L.pmaf_select_clear_tracked(self._h, _p(o), _pi(self._first(first)), float(margin), int(horizon),
+                                                   1 if skip_trailing else 0, _pi(pv), 1 if adopt else 0, _pi(out["pick"]),
+                                                   _pi(out["rule"]), _pi(out["n_clear"]), _p(out["cost"]),
+                                                   _p(out["clearance"]), _pi(out["first_violation"])))
+        return {k: (v[0].item() if self.P == 1 else v) for k, v in out.items()}
 
     def launch_config(self):
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
