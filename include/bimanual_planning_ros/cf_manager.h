@@ -779,6 +779,9 @@ class CfManager {
   // ignored; the radii stay the creation list's. An empty list detaches. The live list keeps steering the real step and
   // the audits. std::runtime_error where the handle's rollout kernel cannot follow tracks (more than 60 field obstacles,
   // another arithmetic policy), std::invalid_argument on a list of another size.
+  // (pmaf_couple_obstacle_tracks, the tracks' device-side source, takes them from ANOTHER population of the same handle;
+  // a CfManager has one population per handle, so the facade has no counterpart: two arms in one handle are driven
+  // through the C-ABI or shard.DualArmCoupling.pair_tick(field=...).)
   void setObstacleTracks(const std::vector<std::vector<Obstacle>> &per_step, int first = 0) {
     require();
     const size_t M = (size_t)n_obs_ - 1;

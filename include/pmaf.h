@@ -577,8 +577,7 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  * the other arithmetic policies; pmaf_evaluate_paths_tracked and pmaf_select_clear_tracked (below) audit and select
  * against the tracks, every other audit and selection -- pmaf_evaluate_paths, pmaf_evaluate_path, pmaf_select_clear,
  * the cross audits, the joint selections pmaf_select_pair_clear / pmaf_select_clear_tracks -- keeps the live list's
- * straight lines and does not see them; the tracks come from the host only (no device-side source like pmaf_couple_tracks); the planner node
- * (planner_node.h) does not use them.
+ * straight lines and does not see them; the planner node (planner_node.h) does not use them.
  * pmaf_set_obstacle_tracks: tracks [P][max_len][M][6] (M = n_obstacles - 1; x y z vx vy vz), len [P]; takes effect from
  *   the next pmaf_start / pmaf_tick and stays until replaced; every population's offset becomes 0. tracks == NULL,
  *   len == NULL or every len == 0 detaches. A value inside len that is NaN or outside the supported numeric range,
@@ -589,10 +588,55 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  *   along the same prediction by one point per tick uploads P integers instead of the tracks. PMAF_ERR_STATE while no
  *   tracks are attached.
  * pmaf_get_obstacle_tracks: what the last launched rollout used (waits for it): len [P], first [P] (may be NULL) and
- *   -- tracks != NULL -- tracks [P][max_len][M][6]; PMAF_ERR_INVALID when max_len is shorter than one of them. */
+ *   -- tracks != NULL -- tracks [P][max_len][M][6]; PMAF_ERR_INVALID when max_len is shorter than one of them. For a
+ *   coupled population (below) that is what the last launched rollout was composed: len = max_prediction_steps (0
+ *   before the first composed launch and while no source has a selection), first = 0.
+ * pmaf_couple_obstacle_tracks: the device-side source of the tracks -- field obstacles that ride on ANOTHER population's
+ *   selected path (the other arm's gripper, its carried object, spheres along its forearm), without the host round trip
+ *   of reading that path back and uploading tracks every tick. src_pop [P][M], scale [P][M], anchor [P][M][3].
+ *   src_pop[p][i] = q >= 0 attaches field obstacle i of population p to the selected path of population q, -1 attaches
+ *   nothing; a population with at least one attached column is COUPLED. src_pop == NULL uncouples everything.
+ *   Source path. In front of every rollout launch the selected path of each source q is taken exactly as
+ *   pmaf_couple_tracks takes it: the path of agent best_idx[q] as it lies in the path buffer after the tick's selection
+ *   (after pmaf_adopt_best, if the caller adopts) and before the rollout overwrites it, from point `shift` on -- with n
+ *   that path's n_points clamped to [1, max_prediction_steps], y_0 is its point min(shift, n - 1) and n_c = max(n - shift,
+ *   1) --; at pmaf_reset_agents in the five-call tick, otherwise at the launch; pmaf_set_initial_position discards what
+ *   was taken. While q has no selection yet its columns count as unattached; if that holds for every attached column of
+ *   p, p has L = 0 and rolls out untracked.
+ *   Composed tracks. Otherwise a coupled population gets L = max_prediction_steps points and offset 0:
+ *     attached column i, k < n_c:   position x_k = RN(anchor + RN(scale * y_k)) per component (one rounded multiply, one
+ *                                   rounded add, no contraction);
+ *     attached column i, k >= n_c:  position x_{n_c - 1};
+ *     attached column, velocity:    u_k = RN(RN(x_{k+1} - x_k) / dt) per component for k < n_c - 1, with dt the handle's
+ *                                   rollout step and the correctly rounded division; +0.0 from k = n_c - 1 on;
+ *     unattached column:            the iterated straight line of the untracked rollout: q_0 the rollout-start list's
+ *                                   position, q_{k+1} = RN(q_k + RN(v dt)), velocity the list's constant v, for all L
+ *                                   points (composed at the launch, after the reset has written the rollout-start list);
+ *     columns >= M:                 zero.
+ *   scale = 1, anchor = 0: the obstacle IS the other end effector; anchor = d: a sphere rigidly attached to it;
+ *   scale = s, anchor = (1 - s) base: a point on the segment base -> end effector, a crude link sphere.
+ *   Unchanged: the radii, the trailing obstacle (line or repulsive track; both couplings may be on together), the latch,
+ *   scoring, the real step -- which still reads the live list, so the caller keeps those rows sensible -- and the
+ *   stepping API.
+ *   Uploaded tracks and the offset -- nothing is silently ignored: coupling a population that has uploaded tracks
+ *   (len > 0) is PMAF_ERR_STATE; pmaf_set_obstacle_tracks with len[p] > 0, or pmaf_set_obstacle_track_offset with
+ *   first[p] != 0, for a coupled p is PMAF_ERR_INVALID. Uncoupled populations of the same handle keep their uploaded
+ *   tracks and offsets (the shared device buffer's stride becomes max(upload max_len, max_prediction_steps)).
+ *   pmaf_evaluate_paths_tracked / pmaf_select_clear_tracked on a coupled population read the tracks the LAST LAUNCHED
+ *   rollout followed (the same buffer; nothing newer exists before the next launch), the caller's `first` says how
+ *   many ticks have passed; before the first composed launch L = 0, the untracked result.
+ *   Route as above: PMAF_ERR_STATE with the route's name at the attach, and from pmaf_start / pmaf_tick after a
+ *   reroute. PMAF_ERR_INVALID: q == p, q >= P, q < -1, shift < 0, a NaN or out-of-range scale / anchor entry, scale or
+ *   anchor NULL while src_pop is not. Waits and drains like pmaf_couple_tracks. Couplings are inputs, not planner
+ *   state: the checkpoint blob does not hold them. Coupled handles launch two small kernels more per tick
+ *   (k_fcouple_take, k_fcouple_compose); a handle that never calls this launches exactly what it launched before.
+ *   Limits that remain: the joint selections and the cross audits still see straight lines; no tracks on the
+ *   multi-slot, multi-wave, group, sliced and generic routes; the planner node does not use them. */
 int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len);
 int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first);
 int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len);
+int pmaf_couple_obstacle_tracks(pmaf_planner *h, const int32_t *src_pop /* [P][M] */, const double *scale /* [P][M] */,
+                                const double *anchor /* [P][M][3] */, int32_t shift);
 
 /* ---- audits against the obstacle tracks: the path audit and the clear selection where the rollouts saw the field
  * obstacles (exports added under ABI 7) ----
@@ -601,7 +645,9 @@ int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int3
  * rejected where the line cuts through it, and a path through the place the obstacle turns into is selected as clear.
  * These two calls are exactly pmaf_evaluate_paths' and pmaf_select_clear's contracts with ONE change, the position of a
  * tracked field obstacle. For population p let L = len[p] be the length of the tracks attached NOW -- what the next
- * rollout launch would follow; the setters synchronise, so there is one set of tracks --, f = first[p] when first is
+ * rollout launch would follow; the setters synchronise, so there is one set of tracks; for a population coupled with
+ * pmaf_couple_obstacle_tracks the tracks the LAST LAUNCHED rollout followed, L = 0 before the first composed launch:
+ * the next launch's are composed only in front of it --, f = first[p] when first is
  * given, else the handle's current offset of p, and M = n_obstacles - 1.
  *   tracked field obstacle (L > 0, j < M):  o_j^k = the POSITION of track point min(f + k, L-1), taken verbatim and held
  *              at the end -- the rollout's rule: step k from x_k sees point min(first + k, L-1). The track's velocities

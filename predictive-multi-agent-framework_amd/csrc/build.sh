@@ -30,6 +30,11 @@
 #                        k_ft_select_audit and k_audit_track_ft, compiled with select.o's flags; a unit of its own for the
 #                        same reason, object auditft.o
 #                        (tests/test_tracked_audit.py holds its kernels to no scratch through the resource record)
+#   pmaf_k_fcouple.hip   the obstacle tracks' device-side source (pmaf_couple_obstacle_tracks): k_fcouple_take and
+#                        k_fcouple_compose, compiled with the plain kernel flags (-ffp-contract=off: the composed
+#                        position is one rounded multiply and one rounded add); a unit of its own for the same reason,
+#                        object fcouple.o
+#                        (tests/test_field_couple.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API): handle, tick protocol, repulsive track,
@@ -81,6 +86,7 @@ DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp
 DEPS_TRACK="pmaf_k_w64.hip pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
 DEPS_FTRACK="pmaf_k_w64.hip pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
 DEPS_AUDITFT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_auditft.hpp"   # ... and pmaf_k_auditft.hip
+DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
 FLAGS_CHANGED=0
@@ -96,6 +102,7 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   [ "$src" = pmaf_k_track.hip ] && extra=$DEPS_TRACK
   [ "$src" = pmaf_k_ftrack.hip ] && extra=$DEPS_FTRACK
   [ "$src" = pmaf_k_auditft.hip ] && extra=$DEPS_AUDITFT
+  [ "$src" = pmaf_k_fcouple.hip ] && extra=$DEPS_FCOUPLE
   for d in $src $DEPS_K $extra build.sh; do [ "$d" -nt "$o" ] && stale=1; done
   [ "$FLAGS_CHANGED" = 1 ] && stale=1
   [ "$stale" = 0 ] && return 0
@@ -130,6 +137,7 @@ kcompile select pmaf_k_select.hip
 kcompile pairclear pmaf_k_pairclear.hip
 kcompile auditft pmaf_k_auditft.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
+kcompile fcouple pmaf_k_fcouple.hip
 # (the flags of k_w64_m2_t1: the same body)
 kcompile track pmaf_k_track.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
 kcompile ftrack pmaf_k_ftrack.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
@@ -146,8 +154,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o \
   $(for u in $HOST_UNITS; do echo "$OBJ/$u.o"; done) -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

@@ -175,8 +175,28 @@ static void capture_coupled_tracks(pmaf_planner *h) {
   HIP_CHECK(hipGetLastError());
 }
 
+// the obstacle tracks' device-side source (pmaf_fcouple.hpp): what both of its kernels take
+static FCoupleArgs fcouple_args(pmaf_planner *h) {
+  const pmaf_planner::FieldTrack &f = h->ftrk;
+  return FCoupleArgs{f.d_src.get(), f.d_scale.get(), f.d_anchor.get(), f.d_is_src.get(), h->D.paths, f.d_sel_pts.get(),
+                     f.d_sel_n.get(), f.d_pts.get(), f.d_len.get(), f.d_first.get(), f.stride, f.shift};
+}
+
+// the source populations' selected paths -> the staging buffer, as they lie in the scored buffer right now (stream order)
+static void take_field_sources(pmaf_planner *h) {
+  pmaf_k_launch_fcouple_take(h->D, fcouple_args(h), h->stream);
+  HIP_CHECK(hipGetLastError());
+}
+
 static void launch_rollout(pmaf_planner *h) {
   if (h->ftrk.on()) require_track_route(h, h->route, "rollout launch", FIELD_TRACKS);
+  if (h->ftrk.coupled) {
+    // the take at k_track_from_best's moment (below); the composition here, where obs_start is what the rollout reads
+    if (!h->ftrk.captured) take_field_sources(h);
+    h->ftrk.captured = false;
+    pmaf_k_launch_fcouple_compose(h->D, fcouple_args(h), h->stream);
+    HIP_CHECK(hipGetLastError());
+  }
   if (h->trk.on()) {
     require_track_route(h, h->route, "rollout launch");   // (pmaf_start / pmaf_tick have checked already)
     // before this rollout overwrites the paths -- unless a reset in front of it already has, and took them first
@@ -613,6 +633,7 @@ int pmaf_set_initial_position(pmaf_planner *h, const double *pos) {
     // CfAgent::setPosition = clear + push_back for every predicted agent
     h->paths_gen++;
     h->trk.captured = false;   // (the paths start over: nothing taken from the old ones is followed)
+    h->ftrk.captured = false;
     pmaf_k_launch_restart_paths(D, D.start_pos, h->stream);
     HIP_CHECK(hipGetLastError());
     h->real_pos_h.assign(pos, pos + P * 3);
@@ -768,6 +789,40 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
 }
 
 // ---- obstacle tracks ----
+// The small buffers every launch of k_rollout_w64_ftrack is handed: the lengths and offsets, and the one-point,
+// zero-length repulsive track of a handle without one. Allocated by the first attach or coupling.
+static void reserve_ftrack_aux(pmaf_planner *h) {
+  pmaf_planner::FieldTrack &f = h->ftrk;
+  const int P = h->D.P;
+  if (f.d_len.reserve(sizeof(int32_t) * P)) HIP_CHECK(hipMemsetAsync(f.d_len.get(), 0, sizeof(int32_t) * P, h->stream));
+  if (f.d_first.reserve(sizeof(int32_t) * P)) HIP_CHECK(hipMemsetAsync(f.d_first.get(), 0, sizeof(int32_t) * P, h->stream));
+  if (f.d_no_pts.reserve(sizeof(double) * (size_t)P * 3)) HIP_CHECK(hipMemsetAsync(f.d_no_pts.get(), 0, sizeof(double) * (size_t)P * 3, h->stream));
+  if (f.d_no_len.reserve(sizeof(int32_t) * P)) HIP_CHECK(hipMemsetAsync(f.d_no_len.get(), 0, sizeof(int32_t) * P, h->stream));
+}
+
+// Grow the points' buffer to `need` points per population and KEEP what it holds (the host has no copy of the points): a
+// coupled handle's buffer is shared between the composed populations and the uploaded ones, and either side may outgrow
+// it while the other's points are still followed. The caller has drained the stream.
+static void grow_ftrack_keeping(pmaf_planner *h, int need) {
+  pmaf_planner::FieldTrack &f = h->ftrk;
+  const int P = h->D.P, old = f.stride;
+  if (f.d_pts.get() && need <= old) return;
+  std::vector<double> was;
+  if (f.d_pts.get() && old > 0) {
+    was.resize((size_t)P * old * PMAF_FTRACK_POINT);
+    h->download(was.data(), f.d_pts.get(), was.size());
+  }
+  f.stride = 0;   // (a failed allocation leaves an empty buffer)
+  f.d_pts.reserve(sizeof(double) * (size_t)P * need * PMAF_FTRACK_POINT);
+  f.stride = need;
+  std::vector<double> pts((size_t)P * need * PMAF_FTRACK_POINT, 0.0);
+  if (!was.empty())
+    for (int p = 0; p < P; p++)
+      std::memcpy(pts.data() + (size_t)p * need * PMAF_FTRACK_POINT, was.data() + (size_t)p * old * PMAF_FTRACK_POINT,
+                  sizeof(double) * (size_t)old * PMAF_FTRACK_POINT);
+  h->upload(f.d_pts.get(), pts.data(), pts.size());
+}
+
 int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len) {
   return guarded([&] {
     REQUIRE(h, "pmaf_set_obstacle_tracks: NULL handle");
@@ -780,6 +835,7 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
       REQUIRE(max_len >= 1, "pmaf_set_obstacle_tracks: max_len must be >= 1");
       for (int p = 0; p < P; p++) {
         REQUIRE(len[p] >= 0 && len[p] <= max_len, "pmaf_set_obstacle_tracks: need 0 <= len <= max_len");
+        REQUIRE(len[p] == 0 || !f.is_coupled(p), "pmaf_set_obstacle_tracks: the population's tracks come from pmaf_couple_obstacle_tracks (len must be 0)");
         check_range(tracks + (size_t)p * max_len * M * 6, (size_t)len[p] * M * 6, "pmaf_set_obstacle_tracks: tracks");
         any = any || len[p] > 0;
       }
@@ -789,6 +845,30 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
     f.attached = any;
     f.first.assign(P, 0);
     f.len.assign(P, 0);
+    if (f.coupled) {
+      // the coupled populations' points, len and first are the device's (k_fcouple_compose): the others' are replaced one
+      // population at a time, and a buffer that has to grow keeps what it holds
+      for (int p = 0; p < P && any; p++) f.len[p] = len[p];
+      if (any) grow_ftrack_keeping(h, (int)max_len);
+      std::vector<double> pts((size_t)f.stride * PMAF_FTRACK_POINT);
+      const int32_t zero = 0;
+      for (int p = 0; p < P; p++) {
+        if (f.is_coupled(p)) continue;
+        if (any) {
+          std::fill(pts.begin(), pts.end(), 0.0);
+          for (int k = 0; k < f.len[p]; k++) {
+            const double *src = tracks + ((size_t)p * max_len + k) * M * 6;
+            double *dst = pts.data() + (size_t)k * PMAF_FTRACK_POINT;
+            for (int i = 0; i < M; i++)
+              for (int c = 0; c < 6; c++) dst[c * PMAF_FTRACK_LANES + i] = src[i * 6 + c];
+          }
+          h->upload(f.d_pts.get() + (size_t)p * f.stride * PMAF_FTRACK_POINT, pts.data(), pts.size());
+        }
+        h->upload(f.d_len.get() + p, &f.len[p], 1);
+        h->upload(f.d_first.get() + p, &zero, 1);
+      }
+      return;
+    }
     if (!any) {
       set_tracked(h, false, "pmaf_set_obstacle_tracks", FIELD_TRACKS);
       if (f.d_len.get()) {   // (the getter reads them)
@@ -801,10 +881,7 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
     // the device layout (pmaf_ftrack.hpp): [P][stride][6][64], transposed here; a population's points lie at its own
     // stride, so a shorter upload into a grown buffer leaves the tail of the longer one behind it, never read
     if (f.d_pts.reserve(sizeof(double) * (size_t)P * std::max(f.stride, (int)max_len) * PMAF_FTRACK_POINT)) f.stride = std::max(f.stride, (int)max_len);
-    f.d_len.reserve(sizeof(int32_t) * P);
-    f.d_first.reserve(sizeof(int32_t) * P);
-    if (f.d_no_pts.reserve(sizeof(double) * (size_t)P * 3)) HIP_CHECK(hipMemsetAsync(f.d_no_pts.get(), 0, sizeof(double) * (size_t)P * 3, h->stream));
-    if (f.d_no_len.reserve(sizeof(int32_t) * P)) HIP_CHECK(hipMemsetAsync(f.d_no_len.get(), 0, sizeof(int32_t) * P, h->stream));
+    reserve_ftrack_aux(h);
     std::vector<double> pts((size_t)P * f.stride * PMAF_FTRACK_POINT, 0.0);
     for (int p = 0; p < P; p++)
       for (int k = 0; k < f.len[p]; k++) {
@@ -819,6 +896,81 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
   });
 }
 
+int pmaf_couple_obstacle_tracks(pmaf_planner *h, const int32_t *src_pop, const double *scale, const double *anchor, int32_t shift) {
+  return guarded([&] {
+    REQUIRE(h, "pmaf_couple_obstacle_tracks: NULL handle");
+    h->use_device();
+    require_drained(h, "pmaf_couple_obstacle_tracks");
+    pmaf_planner::FieldTrack &f = h->ftrk;
+    const int P = h->D.P, M = h->D.n_obs - 1, cap = h->D.cap;
+    bool any = false;
+    std::vector<char> pc((size_t)P, 0);
+    if (src_pop) {
+      REQUIRE(scale && anchor, "pmaf_couple_obstacle_tracks: scale and anchor must be given with src_pop");
+      REQUIRE(shift >= 0, "pmaf_couple_obstacle_tracks: shift must be >= 0");
+      for (int p = 0; p < P; p++)
+        for (int i = 0; i < M; i++) {
+          const int32_t q = src_pop[(size_t)p * M + i];
+          REQUIRE(q >= -1 && q < P && q != p, "pmaf_couple_obstacle_tracks: src_pop must be another population of this handle (or -1)");
+          if (q >= 0) pc[p] = 1;
+        }
+      check_range(scale, (size_t)P * M, "pmaf_couple_obstacle_tracks: scale");
+      check_range(anchor, (size_t)P * M * 3, "pmaf_couple_obstacle_tracks: anchor");
+      for (int p = 0; p < P; p++) {
+        any = any || pc[p];
+        if (pc[p] && f.attached && f.len[p] > 0)
+          fail(PMAF_ERR_STATE, "pmaf_couple_obstacle_tracks: the population has uploaded obstacle tracks (detach them with pmaf_set_obstacle_tracks first)");
+      }
+    }
+    if (any) set_tracked(h, true, "pmaf_couple_obstacle_tracks", FIELD_TRACKS);
+    sync(h);   // a running rollout still reads the buffers
+    // populations that stop being coupled go back to "no tracks"; the uploaded ones keep theirs
+    std::vector<char> was = f.coupled ? f.pop_coupled : std::vector<char>((size_t)P, 0);
+    f.captured = false;
+    if (!any) {
+      f.coupled = false;
+      f.src.clear(); f.pop_coupled.clear(); f.shift = 0;
+      const int32_t zero = 0;
+      for (int p = 0; p < P; p++)
+        if (was[p]) { h->upload(f.d_len.get() + p, &zero, 1); h->upload(f.d_first.get() + p, &zero, 1); }
+      if (!f.attached) set_tracked(h, false, "pmaf_couple_obstacle_tracks", FIELD_TRACKS);
+      return;
+    }
+    reserve_ftrack_aux(h);
+    grow_ftrack_keeping(h, std::max(cap, 1));
+    f.d_src.reserve(sizeof(int32_t) * (size_t)P * PMAF_FTRACK_LANES);
+    f.d_scale.reserve(sizeof(double) * (size_t)P * PMAF_FTRACK_LANES);
+    f.d_anchor.reserve(sizeof(double) * (size_t)P * 3 * PMAF_FTRACK_LANES);
+    f.d_is_src.reserve(sizeof(int32_t) * P);
+    f.d_sel_n.reserve(sizeof(int32_t) * P);
+    f.d_sel_pts.reserve(sizeof(double) * (size_t)P * cap * 3);
+    std::vector<int32_t> src((size_t)P * PMAF_FTRACK_LANES, -1), is_src((size_t)P, 0), zeros((size_t)P, 0);
+    std::vector<double> sc((size_t)P * PMAF_FTRACK_LANES, 0.0), an((size_t)P * 3 * PMAF_FTRACK_LANES, 0.0);
+    for (int p = 0; p < P; p++)
+      for (int i = 0; i < M && i < PMAF_FTRACK_LANES; i++) {   // (the route has M <= 60)
+        const int32_t q = src_pop[(size_t)p * M + i];
+        src[(size_t)p * PMAF_FTRACK_LANES + i] = q;
+        if (q >= 0) is_src[q] = 1;
+        sc[(size_t)p * PMAF_FTRACK_LANES + i] = scale[(size_t)p * M + i];
+        for (int c = 0; c < 3; c++) an[((size_t)p * 3 + c) * PMAF_FTRACK_LANES + i] = anchor[((size_t)p * M + i) * 3 + c];
+      }
+    f.coupled = true;
+    f.src.assign(src_pop, src_pop + (size_t)P * M);
+    f.pop_coupled = pc;
+    f.shift = shift;
+    h->upload(f.d_src.get(), src.data(), src.size());
+    h->upload(f.d_scale.get(), sc.data(), sc.size());
+    h->upload(f.d_anchor.get(), an.data(), an.size());
+    h->upload(f.d_is_src.get(), is_src.data(), is_src.size());
+    h->upload(f.d_sel_n.get(), zeros.data(), zeros.size());   // (nothing taken yet)
+    HIP_CHECK(hipMemsetAsync(f.d_sel_pts.get(), 0, sizeof(double) * (size_t)P * cap * 3, h->stream));
+    // L = 0 until the first composed launch, for the populations that are coupled now or were before
+    const int32_t zero = 0;
+    for (int p = 0; p < P; p++)
+      if (pc[p] || was[p]) { h->upload(f.d_len.get() + p, &zero, 1); h->upload(f.d_first.get() + p, &zero, 1); }
+  });
+}
+
 int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first) {
   return guarded([&] {
     REQUIRE(h && first, "pmaf_set_obstacle_track_offset: NULL argument");
@@ -828,6 +980,8 @@ int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first) {
     const int P = h->D.P;
     for (int p = 0; p < P; p++) REQUIRE(first[p] >= 0, "pmaf_set_obstacle_track_offset: first must be >= 0");
     if (!f.on()) fail(PMAF_ERR_STATE, "pmaf_set_obstacle_track_offset: no obstacle tracks are attached (pmaf_set_obstacle_tracks)");
+    for (int p = 0; p < P; p++)
+      REQUIRE(first[p] == 0 || !f.is_coupled(p), "pmaf_set_obstacle_track_offset: the population's tracks come from pmaf_couple_obstacle_tracks (first must be 0)");
     f.first.assign(first, first + P);
     h->upload(f.d_first.get(), f.first.data(), (size_t)P);   // (stream order: behind a running rollout)
   });
@@ -957,6 +1111,7 @@ int pmaf_reset_agents(pmaf_planner *h, const double *pos, const double *vel, con
       if (sl.pack_pending) { HIP_CHECK(hipEventSynchronize(sl.ev_pack)); sl.pack_pending = false; }
     // coupled tracks: the reset below cuts every path to its first point, so the selected paths are taken here
     if (h->trk.coupled) { capture_coupled_tracks(h); h->trk.captured = true; }
+    if (h->ftrk.coupled) { take_field_sources(h); h->ftrk.captured = true; }
     ResidentGuard resident_guard{h};
     const double *live = stage_live_obstacles_zero_copy(h, obstacles);
     ManagerArgs A{};

@@ -23,6 +23,7 @@
 #include "pmaf_route.hpp"
 #include "pmaf_track.hpp"
 #include "pmaf_ftrack.hpp"
+#include "pmaf_fcouple.hpp"
 
 using namespace pmaf;
 
@@ -283,7 +284,19 @@ struct pmaf_planner {
     int stride = 0;                               // points per population the device buffer holds (>= 1 once allocated)
     std::vector<int32_t> len, first;
     bool attached = false;                        // some len > 0
-    bool on() const { return attached; }
+    // the device-side source (pmaf_couple_obstacle_tracks, pmaf_fcouple.hpp): field obstacles that ride on another
+    // population's selected path. The coupled populations' points, len (cap or 0) and first (0) are written on the
+    // device -- k_fcouple_take at the capture moment of the repulsive coupling, k_fcouple_compose in front of every
+    // rollout launch --; the host's len / first of such a population stay 0. stride >= cap while coupled.
+    bool coupled = false;
+    bool captured = false;                        // as Track::captured: the selected paths were taken in front of a reset
+    std::vector<int32_t> src;                     // [P][M], -1: not attached
+    std::vector<char> pop_coupled;                // [P]: some column of the population is attached
+    int shift = 0;
+    DeviceBuf<int32_t> d_src, d_is_src, d_sel_n;  // [P][64], [P], [P]
+    DeviceBuf<double> d_scale, d_anchor, d_sel_pts;   // [P][64], [P][3][64], [P][cap][3]
+    bool is_coupled(int p) const { return coupled && pop_coupled[(size_t)p] != 0; }
+    bool on() const { return attached || coupled; }
   } ftrk;
   double *d_reset_in = nullptr; // [P][6]
   int32_t *d_agent_id = nullptr;// [P]

@@ -84,6 +84,7 @@ SYMBOLS = {
     "pmaf_set_obstacle_tracks": (C.c_int, [_V, _dp, _ip, C.c_int32]),
     "pmaf_set_obstacle_track_offset": (C.c_int, [_V, _ip]),
     "pmaf_get_obstacle_tracks": (C.c_int, [_V, _dp, _ip, _ip, C.c_int32]),
+    "pmaf_couple_obstacle_tracks": (C.c_int, [_V, _ip, _dp, _dp, C.c_int32]),
     "pmaf_evaluate_paths_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, _dp, _ip, _ip, _ip, _dp]),
     "pmaf_select_clear_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp,
                                             _dp, _ip]),
@@ -841,6 +842,19 @@ class PmafPlanner:
         buf = np.zeros((self.P, m, M, 6))
         self._chk(self.L.pmaf_get_obstacle_tracks(self._h, _p(buf), _pi(ln), _pi(first), m))
         return [buf[p, :ln[p]].copy() for p in range(self.P)], first
+
+    def couple_obstacle_tracks(self, src_pop, scale=None, anchor=None, shift=0):
+        """src_pop [P][M] (-1: not attached) or None to uncouple: field obstacle i of population p rides on the selected
+        path of population src_pop[p][i], at anchor + scale * point (pmaf_couple_obstacle_tracks). scale [P][M] (or one
+        number for all; default 1), anchor [P][M][3] (or one [3] for all; default 0)."""
+        if src_pop is None:
+            self._chk(self.L.pmaf_couple_obstacle_tracks(self._h, None, None, None, 0))
+            return
+        M = self.n_obs - 1
+        src = np.ascontiguousarray(np.broadcast_to(np.asarray(src_pop, dtype=np.int32), (self.P, M)))
+        sc = np.ascontiguousarray(np.broadcast_to(_d(1.0 if scale is None else scale), (self.P, M)))
+        an = np.ascontiguousarray(np.broadcast_to(_d(np.zeros(3) if anchor is None else anchor), (self.P, M, 3)))
+        self._chk(self.L.pmaf_couple_obstacle_tracks(self._h, _pi(src), _p(sc), _p(an), int(shift)))
 
     # -- audits against the obstacle tracks (include/pmaf.h "audits against the obstacle tracks") --
     def _first(self, first):

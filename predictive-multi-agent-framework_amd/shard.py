@@ -136,7 +136,7 @@ class DualArmCoupling:
         return obs
 
     def pair_tick(self, planner, dt, cost_gains, ws, margin, agent_radius=0.05, advance=None, late=None, adopt=False,
-                  clear=None, tracks=None):
+                  clear=None, tracks=None, field=None):
         """One tick of both arms as populations 0 / 1 of ONE handle, the two winners picked TOGETHER: the node's
         five-call sequence with pmaf_select_pair in it (include/pmaf.h "cross audit") --
         stop -> evaluate -> select_pair -> move_real(agent_id = the pair) -> reset -> start. The pair is the cheapest
@@ -158,11 +158,30 @@ class DualArmCoupling:
         tracks = shift: the rollouts this tick starts follow the other arm's selected path from point `shift` on instead of
         the sphere at rest (pmaf_couple_tracks, include/pmaf.h "repulsive track"; with adopt=True the pair's paths, else
         evaluate's own selections). coupled_obstacles is left as it is: the sphere at the last set-point stays in the
-        live list for the real step. The coupling stays on the handle until planner.couple_tracks(None). None: as before."""
+        live list for the real step. The coupling stays on the handle until planner.couple_tracks(None). None: as before.
+        field = dict(shift=s, attach=[(column, scale, anchor), ...]): the listed field obstacles of EACH arm's list ride on
+        the other arm's selected path from point s on, at anchor + scale * point (pmaf_couple_obstacle_tracks,
+        include/pmaf.h "obstacle tracks"): the circular field steers the rollouts around the other arm's gripper, its
+        load, spheres along its forearm. Those rows of the live list stay the caller's (the real step reads them). The
+        planner is called only when the setting changes; the coupling stays on the handle until
+        planner.couple_obstacle_tracks(None). None: as before."""
         assert planner.P == 2, "pair_tick drives the two populations of one handle"
         if tracks is not None and getattr(self, "_track_shift", None) != int(tracks):
             planner.couple_tracks([1, 0], int(tracks))
             self._track_shift = int(tracks)
+        if field is not None:
+            key = (int(field.get("shift", 0)), tuple((int(c), float(s), tuple(float(v) for v in a)) for c, s, a in field["attach"]))
+            if getattr(self, "_field_key", None) != key:
+                M = planner.n_obs - 1
+                src = np.full((2, M), -1, dtype=np.int32)
+                scale = np.ones((2, M))
+                anchor = np.zeros((2, M, 3))
+                for c, s, a in key[1]:
+                    src[0, c], src[1, c] = 1, 0
+                    scale[:, c] = s
+                    anchor[:, c] = a
+                planner.couple_obstacle_tracks(src, scale, anchor, key[0])
+                self._field_key = key
         planner.stop()
         best = planner.evaluate(cost_gains, ws)
         if clear is not None:
