@@ -154,7 +154,10 @@ int pmaf_abi_version(void);
 #define PMAF_EVAL_ORDER_DOT_RIGHT 1
 int pmaf_eval_order(void);
 
-/* CfManager::setInitialPosition, B/src/cf_manager.cpp:226-236. pos [P][3] */
+/* CfManager::setInitialPosition, B/src/cf_manager.cpp:226-236. pos [P][3]. Every path restarts at pos. A pmaf_start
+ * right behind it launches from the population's reset state (the velocity of the last reset; the creation state before
+ * any), not from each agent's own last velocity as the reference's threads would after earlier rollouts: identical on a
+ * fresh handle and in front of a tick, whose reset hands every agent the real agent's velocity. */
 int pmaf_set_initial_position(pmaf_planner *h, const double *pos);
 /* CfManager::setRealEEAgentPosition, B/src/cf_manager.cpp:216-218 -> RealCfAgent::setPosition = push_back
  * (B/src/cf_agent.cpp:44-46): the measured position becomes the real agent's latest one (closed loop: the node calls it
@@ -546,10 +549,16 @@ int pmaf_select_clear_tracks(pmaf_planner *h, int32_t pop, const double *obstacl
  *   uncouples. A coupling and an uploaded track on the same population: the coupling wins while it is set. In the
  *   five-call tick pmaf_reset_agents cuts every path to its first point before pmaf_start launches the rollout: on a
  *   coupled handle it takes the selected paths first (after pmaf_adopt_best, if the caller adopts), and the rollout
- *   pmaf_start launches follows those; pmaf_set_initial_position discards what was taken. Coupled
+ *   pmaf_start launches follows those; pmaf_set_initial_position discards what was taken, and so does a call of
+ *   pmaf_couple_tracks (the launch then takes from the paths as they lie: after a reset, their first point). An upload
+ *   (pmaf_set_repulsive_track) between pmaf_reset_agents and pmaf_start changes the uncoupled populations' tracks only:
+ *   what was taken for the coupled ones stays and is followed. Coupled
  *   handles launch one small copy kernel between the manager kernel and the rollout; others keep the two-launch tick.
  * pmaf_get_repulsive_track: the tracks the last launched rollout used (waits for it): len [P], and -- track != NULL --
- *   track [P][max_len][3]; PMAF_ERR_INVALID when max_len is shorter than one of them. */
+ *   track [P][max_len][3]; PMAF_ERR_INVALID when max_len is shorter than one of them. An uploaded population shows
+ *   what is attached now, cut to max_prediction_steps points. A coupled population shows L = 0 from a call of
+ *   pmaf_set_repulsive_track / pmaf_couple_tracks until its track is taken again, and between pmaf_reset_agents and
+ *   pmaf_start already the track taken for the launch to come. */
 int pmaf_set_repulsive_track(pmaf_planner *h, const double *track, const int32_t *len, int32_t max_len);
 int pmaf_couple_tracks(pmaf_planner *h, const int32_t *src_pop, int32_t shift);
 int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32_t max_len);
@@ -601,7 +610,8 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  *   (after pmaf_adopt_best, if the caller adopts) and before the rollout overwrites it, from point `shift` on -- with n
  *   that path's n_points clamped to [1, max_prediction_steps], y_0 is its point min(shift, n - 1) and n_c = max(n - shift,
  *   1) --; at pmaf_reset_agents in the five-call tick, otherwise at the launch; pmaf_set_initial_position discards what
- *   was taken. While q has no selection yet its columns count as unattached; if that holds for every attached column of
+ *   was taken, and so does a call of pmaf_couple_obstacle_tracks. While q has no selection yet its columns count as
+ *   unattached; if that holds for every attached column of
  *   p, p has L = 0 and rolls out untracked.
  *   Composed tracks. Otherwise a coupled population gets L = max_prediction_steps points and offset 0:
  *     attached column i, k < n_c:   position x_k = RN(anchor + RN(scale * y_k)) per component (one rounded multiply, one
@@ -710,7 +720,9 @@ int pmaf_get_costs(pmaf_planner *h, double *costs);
 int pmaf_get_path_lengths(pmaf_planner *h, double *out);
 /* CfAgent::getMinObsDist, [P][N] */
 int pmaf_get_min_obs_dist(pmaf_planner *h, double *out);
-/* getAgentSuccess, B/src/cf_manager.cpp:208-214, [P][N] (0/1) */
+/* getAgentSuccess, B/src/cf_manager.cpp:208-214, [P][N] (0/1): written by a rollout for the agents that took a step in
+ * it (B/src/cf_agent.cpp:330-337); a reset, a restart of the paths and a rollout in which the agent took no step leave
+ * the flag of the last rollout in which it did */
 int pmaf_get_success(pmaf_planner *h, int32_t *out);
 /* CfAgent::getVelocity of every predicted agent, [P][N][3] */
 int pmaf_get_agent_velocities(pmaf_planner *h, double *out);

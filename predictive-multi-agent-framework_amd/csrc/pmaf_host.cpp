@@ -153,7 +153,24 @@ static void upload_tracks(pmaf_planner *h) {
   if (t.coupled) need = std::max(need, h->D.cap);
   t.d_len.reserve(sizeof(int32_t) * P);
   t.d_src.reserve(sizeof(int32_t) * P);
-  if (t.d_pts.reserve(sizeof(double) * (size_t)P * need * 3)) t.stride = need;   // (grows exactly when need > stride)
+  const bool grew = t.d_pts.reserve(sizeof(double) * (size_t)P * need * 3);   // (grows exactly when need > stride)
+  if (grew) t.stride = need;
+  // An upload between pmaf_reset_agents and pmaf_start of a coupled handle: the coupled populations' tracks were taken in
+  // front of the reset, the paths they came from are cut, and the launch will not take them again -- they stay, and only
+  // the other populations' parts are rewritten (coupled: stride >= cap >= up_max, the buffer did not grow; the coupling
+  // itself is unchanged, pmaf_couple_tracks drops `captured`)
+  if (t.coupled && t.captured && !grew) {
+    std::vector<double> one((size_t)t.stride * 3);
+    for (int p = 0; p < P; p++) {
+      if (t.src[p] >= 0) continue;
+      const int32_t n = t.uploaded ? t.up_len[p] : 0;
+      std::fill(one.begin(), one.end(), 0.0);
+      if (n > 0) std::memcpy(one.data(), t.up.data() + (size_t)p * t.up_max * 3, sizeof(double) * 3 * (size_t)n);
+      h->upload(t.d_pts.get() + (size_t)p * t.stride * 3, one.data(), one.size());
+      h->upload(t.d_len.get() + p, &n, 1);
+    }
+    return;
+  }
   std::vector<double> pts((size_t)P * t.stride * 3, 0.0);
   std::vector<int32_t> len(P, 0), src(P, -1);
   for (int p = 0; p < P; p++) {

@@ -229,6 +229,56 @@ def test_coupled_ticks(pmaf, oracle, scenes, monkeypatch, shift, style):
         pl.close()
 
 
+def test_upload_between_reset_and_start_keeps_the_taken_tracks(pmaf, oracle, scenes, monkeypatch):
+    """Regression, the shortest form of what tests/test_sequence_gpu.py's seeded sequences found (the model's mutant
+    upload_drops_taken is the library as it was): population 1 follows population 0's
+    selected path; in the five-call tick pmaf_set_repulsive_track (an upload for population 0) comes between
+    pmaf_reset_agents, which took the selected path, and pmaf_start. The upload used to rebuild the whole device buffer
+    -- population 1's length became 0 while the handle still counted the track as taken, so the launch took nothing
+    and population 1 rolled out untracked. The taken track stays: the getter shows it before and after the launch, and
+    population 1's rollout is bit for bit that of a twin handle that made no upload."""
+    scs = ref.dual_scenes(scenes)
+    sc = scs[0]
+    live = np.stack([s["obstacles"] for s in scs])
+    up = ref.tracks_for(sc, *_first_path(oracle, sc))["L2"]
+    twins = [planner(pmaf, monkeypatch, scs) for _ in range(2)]
+    try:
+        got = []
+        for k, pl in enumerate(twins):
+            pl.couple_tracks([-1, 0], 1)
+            pl.start()
+            pl.tick(live, sc["dt"], sc["cost_gains"], sc["ws_limits"])
+            pl.stop()
+            paths, n = pl.paths()
+            b = pl.evaluate(sc["cost_gains"], sc["ws_limits"])
+            pl.move_real(live, sc["dt"], 1, b)
+            pos, vel, _ = pl.real_state()
+            pl.reset_agents(pos, vel, live)
+            taken = ref.coupled_track(paths[0][int(b[0])], int(n[0][int(b[0])]), True, 1)
+            assert len(taken) > 3
+            if k == 0:
+                pl.set_repulsive_track([up, None])
+            for when in ("before", "after"):
+                used = pl.get_repulsive_track()
+                np.testing.assert_array_equal(used[1], taken, err_msg="handle %d, %s the launch: the taken track" % (k, when))
+                np.testing.assert_array_equal(used[0], up if k == 0 else np.zeros((0, 3)), err_msg="handle %d, %s the launch: the upload" % (k, when))
+                pl.start()
+                pl.stop()
+            paths, n = pl.paths()
+            got.append((paths, n))
+        np.testing.assert_array_equal(got[0][1][1], got[1][1][1])
+        np.testing.assert_array_equal(got[0][0][1], got[1][0][1])
+        assert not np.array_equal(got[0][0][0], got[1][0][0])       # (population 0 did follow its upload)
+    finally:
+        for pl in twins:
+            pl.close()
+
+
+def _first_path(oracle, sc):
+    un = reference(oracle, sc, None)
+    return un["paths"][0], int(un["n_points"][0])
+
+
 def _raises(code, fn, *a, **kw):
     with pytest.raises(Exception) as e:
         fn(*a, **kw)
