@@ -60,15 +60,8 @@ __global__ __launch_bounds__(64) void k_rollout_w64_track(DevView D, CostParams 
     const V3 sv = mk(src[3 * n_obs + M], src[4 * n_obs + M], src[5 * n_obs + M]);
     reach = sentinel_reachable(p0, sp, sv, D.zsent_lt[pop], C0, D.cap);
   }
-  // (as in rollout_w64_dispatch: field obstacles at rest with +0.0 velocities and the rel_vel rider's lane idle)
-  bool rest = true;
-  for (int i = lane; i < M; i += 64) {
-    const unsigned long long bx = (unsigned long long)__double_as_longlong(src[3 * n_obs + i]),
-                             by = (unsigned long long)__double_as_longlong(src[4 * n_obs + i]),
-                             bz = (unsigned long long)__double_as_longlong(src[5 * n_obs + i]);
-    rest = rest && ((bx | by | bz) == 0ull);
-  }
-  const bool st = !wave_any(!rest) && (M <= 59 || !reach);
+  // (as in rollout_w64_dispatch: field obstacles at rest and the rel_vel rider's lane idle)
+  const bool st = field_obstacles_at_rest(src, n_obs, M, lane, C0.dt) && (M <= 59 || !reach);
 #define PMAF_BODY(T_) \
   if (st) { \
     if (!reach) rollout_w64_body<1, T_, MATH, 0, DPPSUM, PLAIN, true, false>(D, CP, lane, pop, a); \

@@ -39,8 +39,9 @@ __device__ __forceinline__ auto w64_exp_consts(int lane) {
     return exp_consts_in_vgprs();
   }
 }
-// STATICV (one slot per lane): every field obstacle of the population is at rest with +0.0 velocities and the lane the
-// rel_vel rider needs is idle -- decided per block by the kernel (pmaf_rollout_w64.hpp, NVL)
+// STATICV (one slot per lane): every field obstacle of the population is at rest (+0.0 velocities, no -0.0 coordinate,
+// 0 <= dt < inf: field_obstacles_at_rest) and the lane the rel_vel rider needs is idle -- decided per block by the
+// kernel (pmaf_rollout_w64.hpp, NVL)
 // SLICE (round 6): launches of MORE waves than the device has SIMDs -- 1 025 ... 2 048 agents on this kernel: two waves on
 // half or all of the SIMDs. The issue arbiter serves the older wave first, absolutely: the first n_simds waves run at their
 // stand-alone speed T, the others on the slots left over (0.42 of a wave's rate) and then alone, 1.58 T in all (232 -> 375 us
@@ -301,8 +302,10 @@ __device__ __forceinline__ void rollout_w64_body(const DevView &D, const CostPar
     // a -0.0 coordinate into +0.0), so later steps skip it. (Lanes 63 / 61 of the one-slot kernel hold the goal with
     // velocity -0.0: the update leaves it bit for bit.)
     // (one slot per lane: unconditionally -- for obstacles at rest every further application is the identity, and
-    // three multiply-adds are cheaper than a branch in the middle of the tail)
-    if (PRE) O.p[0] = O.p[0] + O.v[0] * C.dt;
+    // three multiply-adds are cheaper than a branch in the middle of the tail. The STATICV body without the repulsive
+    // obstacle drops it: the FIRST application is the identity there too, field_obstacles_at_rest says so -- three
+    // multiplies and three adds per step, -ffp-contract=off. With the obstacle in lane 60 it stays: that lane moves.)
+    if (PRE && !(STATICV && SENT == 0)) O.p[0] = O.p[0] + O.v[0] * C.dt;
     if (TRACK && SENT == 1) {   // lane 60 takes the track's point in place of o + v dt (three selects, no masked block)
       const bool tl = PMAF_LANE(trk_m);
       O.p[0].x = tl ? trk_next.x : O.p[0].x; O.p[0].y = tl ? trk_next.y : O.p[0].y; O.p[0].z = tl ? trk_next.z : O.p[0].z;
@@ -439,17 +442,10 @@ __device__ __forceinline__ void rollout_w64_dispatch(const DevView &D, const Cos
     const V3 p0 = mk(D.start_pos[pop * 3], D.start_pos[pop * 3 + 1], D.start_pos[pop * 3 + 2]);
     const PopConst C0 = D.C;
     const bool reach = sentinel_reachable(p0, sp, sv, D.zsent_lt[pop], C0, D.cap);
-    // field obstacles at rest with +0.0 velocities (bit patterns: v - (-0.0) would turn a -0.0 component of v into +0.0),
-    // and the rider's lane idle (lane 60; 59 when lane 60 holds the repulsive obstacle): the loops with one
-    // normalisation sequence less per step
-    bool rest = true;
-    for (int i = lane; i < M; i += 64) {
-      const unsigned long long bx = (unsigned long long)__double_as_longlong(src[3 * n_obs + i]),
-                               by = (unsigned long long)__double_as_longlong(src[4 * n_obs + i]),
-                               bz = (unsigned long long)__double_as_longlong(src[5 * n_obs + i]);
-      rest = rest && ((bx | by | bz) == 0ull);
-    }
-    const bool st = !wave_any(!rest) && (M <= 59 || !reach);
+    // field obstacles at rest (field_obstacles_at_rest: +0.0 velocities, no -0.0 coordinate, 0 <= dt < inf) and the
+    // rider's lane idle (lane 60; 59 when lane 60 holds the repulsive obstacle): the loops with one normalisation
+    // sequence less per step and, without the repulsive obstacle, no obstacle advance
+    const bool st = field_obstacles_at_rest(src, n_obs, M, lane, C0.dt) && (M <= 59 || !reach);
 #define PMAF_BODY(T) \
     if (st) { \
       if (!reach) rollout_w64_body<TILES, T, MATH, 0, DPPSUM, PLAIN, true, SLICE>(D, CP, lane, pop, a); \

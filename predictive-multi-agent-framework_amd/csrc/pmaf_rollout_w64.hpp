@@ -112,6 +112,29 @@ __device__ __forceinline__ bool sentinel_reachable(V3 p, V3 sent_pos, V3 sent_ve
   return !(d0 > range + reach);  // NaN anywhere: keep testing
 }
 
+// Are the population's M field obstacles (src = its [7][n_obs] start list) at rest in the sense the one-slot kernels'
+// STATICV bodies assume? (wave-uniform; one wave, every lane calls it)
+//   * every velocity component is +0.0 by BIT PATTERN (v - (-0.0) would turn a -0.0 component of v into +0.0),
+//   * no position coordinate has the bit pattern of -0.0, and 0 <= dt < infinity: then predictObstacles'
+//     p + (+0.0) dt is p for every coordinate from the first step on -- (+0.0) dt is a zero (dt = inf: NaN) and p + (+-0)
+//     is p for every p but -0.0 + (+0.0) = +0.0 -- so the SENT == 0 body carries no advance at all (lanes 63 / 61 hold
+//     the goal with velocity -0.0 for the same reason; a -0.0 there stays, with or without the advance).
+// A population that fails any of it takes the bodies that advance every step: slower, never different.
+__device__ __forceinline__ bool field_obstacles_at_rest(const double *src, int n_obs, int M, int lane, double dt) {
+  bool rest = true;
+  for (int i = lane; i < M; i += 64) {
+    const unsigned long long bx = (unsigned long long)__double_as_longlong(src[3 * n_obs + i]),
+                             by = (unsigned long long)__double_as_longlong(src[4 * n_obs + i]),
+                             bz = (unsigned long long)__double_as_longlong(src[5 * n_obs + i]);
+    const unsigned long long px = (unsigned long long)__double_as_longlong(src[i]),
+                             py = (unsigned long long)__double_as_longlong(src[n_obs + i]),
+                             pz = (unsigned long long)__double_as_longlong(src[2 * n_obs + i]);
+    const unsigned long long neg0 = 0x8000000000000000ull;
+    rest = rest && ((bx | by | bz) == 0ull) && (px != neg0) && (py != neg0) && (pz != neg0);
+  }
+  return !wave_any(!rest) && (dt >= 0.0) && (dt < __builtin_huge_val());
+}
+
 // repelForce (B/src/cf_agent.cpp:159-181): only the trailing obstacle repels;
 // in range iff |dist_vec|^2 < zsent_lt (host-computed exact boundary of
 // max(|dist_vec| - (rad + r), 1e-5) < shell). Rare: strict arithmetic in all
