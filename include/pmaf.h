@@ -584,9 +584,11 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  * handle without tracks, launches what it launched before these calls existed.
  * Limits: no tracks on the multi-slot (> 60 field obstacles), multi-wave, group, sliced and generic routes, nor under
  * the other arithmetic policies; pmaf_evaluate_paths_tracked and pmaf_select_clear_tracked (below) audit and select
- * against the tracks, every other audit and selection -- pmaf_evaluate_paths, pmaf_evaluate_path, pmaf_select_clear,
- * the cross audits, the joint selections pmaf_select_pair_clear / pmaf_select_clear_tracks -- keeps the live list's
- * straight lines and does not see them; the planner node (planner_node.h) does not use them.
+ * against the tracks, and pmaf_select_pair_clear_tracked / pmaf_cross_audit_attached (further below) pick and audit the
+ * pair against them and against the spheres a coupling attaches; every other audit and selection -- pmaf_evaluate_paths,
+ * pmaf_evaluate_path, pmaf_select_clear, pmaf_cross_audit and the slacked cross audits, pmaf_select_pair_clear and
+ * pmaf_select_clear_tracks -- keeps the live list's straight lines and does not see them; the planner node
+ * (planner_node.h) does not use them.
  * pmaf_set_obstacle_tracks: tracks [P][max_len][M][6] (M = n_obstacles - 1; x y z vx vy vz), len [P]; takes effect from
  *   the next pmaf_start / pmaf_tick and stays until replaced; every population's offset becomes 0. tracks == NULL,
  *   len == NULL or every len == 0 detaches. A value inside len that is NaN or outside the supported numeric range,
@@ -640,8 +642,10 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  *   anchor NULL while src_pop is not. Waits and drains like pmaf_couple_tracks. Couplings are inputs, not planner
  *   state: the checkpoint blob does not hold them. Coupled handles launch two small kernels more per tick
  *   (k_fcouple_take, k_fcouple_compose); a handle that never calls this launches exactly what it launched before.
- *   Limits that remain: the joint selections and the cross audits still see straight lines; no tracks on the
- *   multi-slot, multi-wave, group, sliced and generic routes; the planner node does not use them. */
+ *   Limits that remain: the joint selection with tracks from the caller (pmaf_select_clear_tracks), the slacked cross
+ *   audits and the C++ facade still see straight lines and the end effectors only (pmaf_select_pair_clear_tracked and
+ *   pmaf_cross_audit_attached, below, see the tracks and the attached spheres); no tracks on the multi-slot, multi-wave,
+ *   group, sliced and generic routes; the planner node does not use them. */
 int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len);
 int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first);
 int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len);
@@ -691,6 +695,60 @@ int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const in
                               int32_t horizon, int32_t skip_trailing, const int32_t *prev_idx, int32_t adopt,
                               int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
                               int32_t *first_violation);
+
+/* ---- joint selection on coupled handles: pairs held to the riding spheres (exports added under ABI 7) ----
+ * pmaf_couple_obstacle_tracks puts spheres of one arm's list on the OTHER arm's selected path (gripper, load, forearm
+ * spheres at anchor + scale * point) and the rollouts bend round them. pmaf_select_pair_clear then picks the pair
+ * against the live list's straight lines and holds the two arms against each other at one point per arm: a pair in
+ * which arm A's end effector passes through the sphere on arm B's forearm is feasible. These two calls audit a pair
+ * (i, j) against the spheres the coupling exists for, riding on the path of the candidate that is being picked -- not on
+ * the last launch's selection, which is stale for it. No reference equivalent.
+ * Terms of a pair. a = pop_a, b = pop_b, M = n_obstacles - 1; src_pop, scale, anchor = the handle's CURRENT coupling,
+ * what pmaf_couple_obstacle_tracks last set (nothing attached on a handle that is not coupled); `shift` is NOT used:
+ * step k of both candidate paths is one instant, as in the cross audit. S_ab = {s < M : src_pop[a][s] == b}, the spheres
+ * of A's list that are parts of arm B; S_ba = {s < M : src_pop[b][s] == a}. xh, yh, K = max(n, m), the hold rule and the
+ * empty-path rule are pmaf_cross_audit's. The terms, in this order:
+ *   term 0:                          the end effectors: u = xh_k, z = yh_k, R_0 = separation
+ *   term 1 + s, s in S_ab ascending: u = xh_k, z = RN(anchor[a][s] + RN(scale[a][s] * yh_k)) per component -- one rounded
+ *                                    multiply, one rounded add, nothing fused: the composer's formula --,
+ *                                    R = RN(radius + r) with radius = pmaf_params.radius, r = obstacles[a][s][6]
+ *   term 1 + M + s, s in S_ba asc.:  u = yh_k, z = RN(anchor[b][s] + RN(scale[b][s] * xh_k)), r = obstacles[b][s][6]
+ *   d2_t   = min over k < K of dot(u - z, u - z) in the build's association (pmaf_eval_order), every operation rounded,
+ *            strict `<` from +infinity, k ascending; a NaN never wins
+ *   gap_t  = sqrt(d2_t) - R_t, +infinity if nothing won
+ *   clearance(i,j) = min over t of gap_t, strict `<` from +infinity in term order: ties go to the smallest term, then
+ *            the smallest k. step(i,j) = the winning term's k; sphere(i,j) = its code 0, 1 + s or 1 + M + s. Nothing
+ *            won, or an empty path: +infinity / -1 / -1. No term has a margin of its own.
+ * With S_ab and S_ba empty this is pmaf_cross_audit bit for bit, and sphere is 0 wherever a step won.
+ *
+ * pmaf_cross_audit_attached: the matrices above on the whole CURRENT paths of pop_a and pop_b. clearance [N][N] is
+ * required; step [N][N] and sphere [N][N] may be NULL. obstacles [P][n_obstacles][7] is range-checked like every list;
+ * only its radii are read. Waits, state rules (none is changed) and validation are pmaf_cross_audit's.
+ *
+ * pmaf_select_pair_clear_tracked: pmaf_select_pair_clear's contract with late == NULL -- window, rules -1 / 0 / 1 / 2,
+ * S, g, record, adopt, waits, the abandoned-tick refusal, outputs and which of them may be NULL -- with two changes.
+ *   Obstacle side. c, fv and clear of both sides are pmaf_select_clear_tracked's with the same first ([P] or NULL, its
+ *     validation and its PMAF_ERR_STATE rule), horizon and skip_trailing: a field obstacle of a population with tracks
+ *     is where the rollouts saw it. Side A's audit also leaves out the columns of S_ab and side B's those of S_ba:
+ *     those spheres ride on the last launch's selection, which is stale for the pair being picked, and the pair side
+ *     replaces them, as it replaces the trailing sphere. Columns attached to a third population, and unattached
+ *     columns, stay as pmaf_select_clear_tracked has them. If nothing is left to audit, c = +infinity and every agent
+ *     is clear.
+ *   Pair side. clearance(i,j) and pair_steps = (step, step) are the attached audit's on the two path sets cut to their
+ *     windows, held to pair_margin.
+ * On a handle without tracks and without coupling the call is pmaf_select_pair_clear(late = NULL) bit for bit, through
+ * the same kernels.
+ * Limits that remain: no `late` (the slack band sees the end effectors only); pmaf_select_clear_tracks, whose side B
+ * comes from the caller, sees neither tracks nor attachments; the C++ facade (one population per handle) uses neither
+ * call. */
+int pmaf_cross_audit_attached(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
+                              double *clearance, int32_t *step, int32_t *sphere);
+int pmaf_select_pair_clear_tracked(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles,
+                                   const int32_t *first, double obstacle_margin, int32_t horizon, int32_t skip_trailing,
+                                   double separation, double pair_margin, const int32_t *prev_pair, int32_t adopt,
+                                   int32_t *pair, int32_t *rule, int32_t *n_feasible, int32_t *n_clear, double *pair_cost,
+                                   double *pair_clearance, double *obstacle_clearance, int32_t *first_violation,
+                                   double *worst_excess, int32_t *pair_steps);
 
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last

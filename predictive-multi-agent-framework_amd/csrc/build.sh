@@ -35,6 +35,11 @@
 #                        position is one rounded multiply and one rounded add); a unit of its own for the same reason,
 #                        object fcouple.o
 #                        (tests/test_field_couple.py holds its kernels to no scratch through the resource record)
+#   pmaf_k_xattach.hip   the cross audit on coupled handles (pmaf_cross_audit_attached / pmaf_select_pair_clear_tracked):
+#                        k_cross_audit_attached on the tile header pmaf_cross_audit.hpp, compiled with the plain kernel
+#                        flags (-ffp-contract=off: the riding sphere is one rounded multiply and one rounded add); a unit
+#                        of its own for the same reason, object xattach.o
+#                        (tests/test_attached_audit.py holds its kernel to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API): handle, tick protocol, repulsive track,
@@ -85,7 +90,8 @@ HFLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-
 DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
 DEPS_TRACK="pmaf_k_w64.hip pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
 DEPS_FTRACK="pmaf_k_w64.hip pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
-DEPS_AUDITFT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_auditft.hpp"   # ... and pmaf_k_auditft.hip
+DEPS_AUDITFT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_auditft.hpp pmaf_xattach.hpp"   # ... and pmaf_k_auditft.hip
+DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach.hip
 DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
@@ -103,6 +109,7 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   [ "$src" = pmaf_k_ftrack.hip ] && extra=$DEPS_FTRACK
   [ "$src" = pmaf_k_auditft.hip ] && extra=$DEPS_AUDITFT
   [ "$src" = pmaf_k_fcouple.hip ] && extra=$DEPS_FCOUPLE
+  [ "$src" = pmaf_k_xattach.hip ] && extra=$DEPS_XATTACH
   for d in $src $DEPS_K $extra build.sh; do [ "$d" -nt "$o" ] && stale=1; done
   [ "$FLAGS_CHANGED" = 1 ] && stale=1
   [ "$stale" = 0 ] && return 0
@@ -138,6 +145,7 @@ kcompile pairclear pmaf_k_pairclear.hip
 kcompile auditft pmaf_k_auditft.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
 kcompile fcouple pmaf_k_fcouple.hip
+kcompile xattach pmaf_k_xattach.hip
 # (the flags of k_w64_m2_t1: the same body)
 kcompile track pmaf_k_track.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
 kcompile ftrack pmaf_k_ftrack.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
@@ -154,8 +162,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o "$OBJ"/xattach.o \
   $(for u in $HOST_UNITS; do echo "$OBJ/$u.o"; done) -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log "$OBJ"/xattach.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

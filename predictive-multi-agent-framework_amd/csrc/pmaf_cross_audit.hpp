@@ -1,6 +1,7 @@
-// pmaf_cross_audit.hpp -- the cross audit's tile, what its two kernels share: k_cross_audit (pmaf_xaudit_kernels.hpp,
-// compiled in pmaf_k_misc.hip) and k_cross_audit_slack (pmaf_k_slack.hip). Both own the same tile and differ only in
-// the steps of B a step of A is held against; this header has the tile's shape (the constants the GPU tests read their
+// pmaf_cross_audit.hpp -- the cross audit's tile, what its three kernels share: k_cross_audit (pmaf_xaudit_kernels.hpp,
+// compiled in pmaf_k_misc.hip), k_cross_audit_slack (pmaf_k_slack.hip) and k_cross_audit_attached (pmaf_k_xattach.hip).
+// All own the same tile and differ only in the steps of B a step of A is held against and in what is staged of a point
+// (the attached audit: the sphere that rides on it); this header has the tile's shape (the constants the GPU tests read their
 // shapes from), its staging into LDS, its prologue and the store of one finished pair. No kernel is defined here.
 //
 // Tile          a block of 256 threads owns T = 32 paths of A x T = 32 paths of B and walks the steps in chunks of
@@ -29,9 +30,11 @@ namespace pmaf {
 #define PMAF_XAUDIT_CHUNK 16      // C: steps staged per pass
 #define PMAF_XAUDIT_THREADS 256
 
-// one tile's chunk of steps [k0, k0 + C) into s[(k * 3 + c) * (T + 1) + path]
-__device__ __forceinline__ void xaudit_stage(double *s, const double *paths, const int *s_n, int first, int count,
-                                             int cap, int k0) {
+// one tile's chunk of steps [k0, k0 + C) into s[(k * 3 + c) * (T + 1) + path]; f(value, c) is what is stored of
+// component c of a point (k_cross_audit_attached, pmaf_k_xattach.hip: the sphere that rides on the point)
+template <typename F>
+__device__ __forceinline__ void xaudit_stage_with(double *s, const double *paths, const int *s_n, int first, int count,
+                                                  int cap, int k0, F f) {
   constexpr int T = PMAF_XAUDIT_TILE, C = PMAF_XAUDIT_CHUNK, TP = T + 1;
   for (int e = threadIdx.x; e < T * C * 3; e += PMAF_XAUDIT_THREADS) {
     const int t = e / (C * 3), r = e - t * (C * 3);
@@ -43,8 +46,14 @@ __device__ __forceinline__ void xaudit_stage(double *s, const double *paths, con
     kk = kk < last ? kk : last;               // hold: an ended path stays at its last point
     kk = kk > 0 ? kk : 0;                     // (an empty path: row 0, overwritten at the end)
     PMAF_BOUND(p >= 0 && kk < cap);
-    s[r * TP + t] = paths[((size_t)p * cap + kk) * 3 + c];
+    s[r * TP + t] = f(paths[((size_t)p * cap + kk) * 3 + c], c);
   }
+}
+
+// ... the points as they lie
+__device__ __forceinline__ void xaudit_stage(double *s, const double *paths, const int *s_n, int first, int count,
+                                             int cap, int k0) {
+  xaudit_stage_with(s, paths, s_n, first, count, cap, k0, [](double v, int) { return v; });
 }
 
 // the prologue: the clamped path lengths of the tile at (a0, b0) into s_na / s_nb [T], the longest of them -- the

@@ -3,6 +3,7 @@
 // cross-audit calls, the joint selection, the link force. None of it runs inside pmaf_tick.
 #include "pmaf_host_impl.hpp"
 #include "pmaf_auditft.hpp"
+#include "pmaf_xattach.hpp"
 
 extern "C" {
 
@@ -340,10 +341,38 @@ static void clamp_slack(const pmaf_planner *h, XAuditSlack *slack, const char *w
   }
 }
 
+// the attached audit (include/pmaf.h "joint selection on coupled handles"): the two populations whose lists' spheres
+// ride on each other's candidate paths, and the staged list [P][7][n_obs] on the device whose radii the terms take. The
+// terms themselves are the coupling's resident rows (pmaf_planner::FieldTrack::d_src / d_scale / d_anchor): nothing is
+// uploaded for the call. The sphere matrix, when wanted, lies where the slacked calls keep their second step matrix.
+struct XAuditAttach {
+  int32_t pop_a, pop_b;
+  const double *list;
+  bool want_sphere;
+};
+// the columns of population p's list that ride on population q's path in the handle's CURRENT coupling, as a mask
+static uint64_t attached_columns(const pmaf_planner *h, int32_t p, int32_t q) {
+  const pmaf_planner::FieldTrack &f = h->ftrk;
+  if (!f.coupled) return 0;
+  const int M = h->D.n_obs - 1;
+  uint64_t m = 0;
+  for (int s = 0; s < M && s < PMAF_FTRACK_LANES; s++)
+    if (f.src[(size_t)p * M + s] == q) m |= (uint64_t)1 << s;
+  return m;
+}
+static XAttachSide attach_side(const pmaf_planner *h, const XAuditAttach &T, int32_t p) {
+  const pmaf_planner::FieldTrack &f = h->ftrk;
+  const double *rad = T.list + ((size_t)p * 7 + 6) * h->D.n_obs;
+  if (!f.coupled) return XAttachSide{nullptr, nullptr, nullptr, rad};
+  return XAttachSide{f.d_src.get() + (size_t)p * PMAF_FTRACK_LANES, f.d_scale.get() + (size_t)p * PMAF_FTRACK_LANES,
+                     f.d_anchor.get() + (size_t)p * 3 * PMAF_FTRACK_LANES, rad};
+}
+
 // the launch: set A against set B into the scratch, the step matrices where they are wanted
 static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *paths_a, const int32_t *len_a, int32_t n_a,
                           const double *paths_b, const int32_t *len_b, int32_t n_b, double separation,
-                          const XAuditSlack *slack, bool want_a, bool want_b, const XAuditWindow *win = nullptr) {
+                          const XAuditSlack *slack, bool want_a, bool want_b, const XAuditWindow *win = nullptr,
+                          const XAuditAttach *att = nullptr) {
   if (win) {   // both sides cut to their windows: the audit kernels read these lengths instead
     PairWindowArgs W{};
     W.n_a = len_a;
@@ -375,6 +404,17 @@ static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *pat
     S.late_b = slack->late_b;
     S.step_b = want_b ? B.step_b : nullptr;
     pmaf_k_launch_cross_audit_slack(S, h->stream);
+  } else if (att) {
+    CrossAuditAttachedArgs T{};
+    T.X = A;
+    T.a = attach_side(h, *att, att->pop_a);
+    T.b = attach_side(h, *att, att->pop_b);
+    T.pop_a = att->pop_a;
+    T.pop_b = att->pop_b;
+    T.M = h->D.n_obs - 1;
+    T.radius = h->D.C.rad;
+    T.sphere = att->want_sphere ? B.step_b : nullptr;
+    pmaf_k_launch_cross_audit_attached(T, h->stream);
   } else {
     pmaf_k_launch_cross_audit(A, h->stream);
   }
@@ -391,7 +431,8 @@ static void xaudit_download(pmaf_planner *h, const XAuditBuf &B, size_t pairs, d
 
 // population pop_a's paths against population pop_b's where they lie; the matrix stays in the scratch
 static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separation, XAuditSlack *slack,
-                                         bool want_a, bool want_b, const char *who, const XAuditWindow *win = nullptr) {
+                                         bool want_a, bool want_b, const char *who, const XAuditWindow *win = nullptr,
+                                         const XAuditAttach *att = nullptr) {
   const DevView &D = h->D;
   if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
     fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
@@ -399,10 +440,10 @@ static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t
   clamp_slack(h, slack, who);
   h->use_device();
   if (!win) sync(h);   // behind the running rollout, like the getters of its results (the joint selection has waited)
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr, win != nullptr);
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr || (att && att->want_sphere), win != nullptr);
   xaudit_launch(h, B, D.paths + (size_t)pop_a * D.N * D.cap * 3, D.n_points + (size_t)pop_a * D.N, D.N,
                 D.paths + (size_t)pop_b * D.N * D.cap * 3, D.n_points + (size_t)pop_b * D.N, D.N, separation, slack, want_a,
-                want_b, win);
+                want_b, win, att);
   return B;
 }
 
@@ -466,6 +507,24 @@ int pmaf_cross_audit(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separ
     REQUIRE(h && clearance, "pmaf_cross_audit: NULL argument");
     const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, step != nullptr, false, "pmaf_cross_audit");
     xaudit_download(h, B, (size_t)h->D.N * h->D.N, clearance, step, nullptr);
+  });
+}
+
+int pmaf_cross_audit_attached(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
+                              double *clearance, int32_t *step, int32_t *sphere) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_cross_audit_attached: NULL argument");
+    const DevView &D = h->D;
+    if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
+      fail(PMAF_ERR_INVALID, "pmaf_cross_audit_attached: need two different populations of the handle");
+    check_range(&separation, 1, "separation");
+    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+    h->use_device();
+    sync(h);   // behind the running rollout; the list's upload below is in stream order behind it
+    const XAuditAttach T{pop_a, pop_b, upload_plan_obstacles(h, obstacles), sphere != nullptr};
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, step != nullptr, false,
+                                                "pmaf_cross_audit_attached", nullptr, &T);
+    xaudit_download(h, B, (size_t)D.N * D.N, clearance, step, sphere);
   });
 }
 
@@ -534,7 +593,11 @@ int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double
 // ---- joint selection (include/pmaf.h, "joint selection: clear of the live list and of each other"):
 // pmaf_select_pair_clear, pmaf_select_clear_tracks. One path for both: the select path's audit (k_select_stage,
 // k_select_audit into its scratch), the cross audit path above with a window, then pmaf_k_pairclear.hip's reduction over
-// what both left on the device. Side B is population pop_b, or -- pop_b < 0 -- the caller's tracks. ----
+// what both left on the device. Side B is population pop_b, or -- pop_b < 0 -- the caller's tracks.
+// pmaf_select_pair_clear_tracked (include/pmaf.h, "joint selection on coupled handles") is the same path with a
+// TrackedCall: the obstacle side is then the tracked selection's audit (k_ft_select_audit, or k_ft_masked_audit where
+// columns of either list ride on the other member of the pair) and the pair side k_cross_audit_attached; a handle
+// without tracks and without such columns launches exactly what pmaf_select_pair_clear launches. ----
 struct PairClearSideB {
   int32_t pop_b, n_tracks;
   const double *tracks;
@@ -551,7 +614,7 @@ struct PairClearOut {
 static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSideB &sb, const double *obstacles,
                               double obstacle_margin, int32_t horizon, int32_t skip_trailing, double separation,
                               double pair_margin, const int32_t *late, const int32_t *prev_pair, int32_t adopt,
-                              const PairClearOut &out, const std::string &who) {
+                              const PairClearOut &out, const std::string &who, const TrackedCall *tracked = nullptr) {
   const DevView &D = h->D;
   const bool tracks = sb.pop_b < 0;
   REQUIRE(horizon >= 1, who + ": horizon must be >= 1");
@@ -569,6 +632,7 @@ static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSid
   check_range(&pair_margin, 1, "pair_margin");
   check_range(&separation, 1, "separation");
   if (tracks && sb.track_cost) check_range(sb.track_cost, (size_t)sb.n_tracks, "track_cost");
+  if (tracked) check_tracked_first(h, *tracked);
   h->use_device();
   require_drained(h, who.c_str());
   sync(h);   // behind the running rollout, like the getters of its results
@@ -584,8 +648,23 @@ static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSid
   S.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;
   S.clr = h->d_sel_clr;
   S.fv = h->d_sel_fv;
-  pmaf_k_launch_select_audit(D, S, h->stream);
+  // (the tracked call: the columns of either list that ride on the OTHER member of the pair are the pair side's)
+  const uint64_t s_ab = tracked ? attached_columns(h, pop_a, sb.pop_b) : 0, s_ba = tracked ? attached_columns(h, sb.pop_b, pop_a) : 0;
+  const bool attached = (s_ab | s_ba) != 0;
+  if (tracked && h->ftrk.on()) {   // (no tracks and no coupling: the untracked audit, whose result it is)
+    const FTrackArgs F = tracked_args(h, *tracked);
+    pmaf_k_launch_select_stage(D, S, h->stream);
+    if (attached) {
+      const uint64_t all = S.n_audit >= 64 ? ~(uint64_t)0 : ((uint64_t)1 << S.n_audit) - 1;
+      pmaf_k_launch_masked_audit_ft(D, S, F, AuditColumns{pop_a, sb.pop_b, all & ~s_ab, all & ~s_ba}, h->stream);
+    } else {
+      pmaf_k_launch_select_audit_ft(D, S, F, h->stream);
+    }
+  } else {
+    pmaf_k_launch_select_audit(D, S, h->stream);
+  }
   HIP_CHECK(hipGetLastError());
+  const XAuditAttach att{pop_a, sb.pop_b, h->d_sel_obs, false};
   // 2., 3. the windowed lengths and the cross audit on them; the matrix stays in the scratch
   const bool want = out.pair_steps != nullptr;
   int32_t keep = 0;   // (cross_audit_tracks takes "this step matrix is wanted" as a pointer)
@@ -593,7 +672,7 @@ static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSid
                                                   late ? &slack : nullptr, nullptr, want ? &keep : nullptr,
                                                   want ? &keep : nullptr, who.c_str(), &win, sb.track_cost)
                              : cross_audit_populations(h, pop_a, sb.pop_b, separation, late ? &slack : nullptr, want, want,
-                                                       who.c_str(), &win);
+                                                       who.c_str(), &win, attached ? &att : nullptr);
   // 4., 5. the joint reduction, the rule, the record and the adopt stores
   const size_t rec_at = select_pairclear_rec(D);
   double *rec = h->sel.host() + rec_at;
@@ -655,6 +734,24 @@ int pmaf_select_pair_clear(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const 
                       PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
                                    first_violation, worst_excess, pair_steps},
                       "pmaf_select_pair_clear");
+  });
+}
+
+int pmaf_select_pair_clear_tracked(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, const int32_t *first,
+                                   double obstacle_margin, int32_t horizon, int32_t skip_trailing, double separation,
+                                   double pair_margin, const int32_t *prev_pair, int32_t adopt, int32_t *pair, int32_t *rule,
+                                   int32_t *n_feasible, int32_t *n_clear, double *pair_cost, double *pair_clearance,
+                                   double *obstacle_clearance, int32_t *first_violation, double *worst_excess,
+                                   int32_t *pair_steps) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && pair, "pmaf_select_pair_clear_tracked: NULL argument");
+    REQUIRE(pop_b >= 0, "pmaf_select_pair_clear_tracked: need two different populations of the handle");
+    const TrackedCall T{first, "pmaf_select_pair_clear_tracked"};
+    select_pair_clear(h, pop_a, PairClearSideB{pop_b, 0, nullptr, nullptr, nullptr}, obstacles, obstacle_margin, horizon,
+                      skip_trailing, separation, pair_margin, nullptr, prev_pair, adopt,
+                      PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
+                                   first_violation, worst_excess, pair_steps},
+                      T.who, &T);
   });
 }
 

@@ -28,6 +28,9 @@
 // k_audit_track_ft   k_audit_track's buffer [P][cap][3][n_obs]: one thread per (population, obstacle); a tracked column
 //                    copies the positions of points min(f + k, L-1), the others run k_audit_track's chain. k_path_audit
 //                    (pmaf_k_misc.hip) then runs unchanged on it.
+// k_ft_masked_audit  k_ft_select_audit's body with the audited columns of two populations given as masks
+//                    (pmaf_xattach.hpp: the joint selection on coupled handles leaves the columns that ride on the other
+//                    member of the pair to its pair side); both kernels are instances of ft_select_audit<COLS>.
 // The list is staged by k_select_stage and the pick is k_select_pick (pmaf_k_select.hip), both unchanged.
 // (The name is k_ft_select_audit, not k_select_audit_ft: tests/test_select_clear.py and tests/test_pair_clear.py find
 // k_select_audit's line of the resource record by substring and expect exactly one.)
@@ -36,6 +39,7 @@
 #include "pmaf_types.hpp"
 #include "pmaf_device.hpp"
 #include "pmaf_auditft.hpp"
+#include "pmaf_xattach.hpp"
 
 using namespace pmaf;
 
@@ -53,7 +57,11 @@ __device__ __forceinline__ void ft_window(const FTrackArgs &F, int pop, int &L, 
   f = f < L - 1 ? f : (L > 0 ? L - 1 : 0);   // clamped before any k is added: first may be INT32_MAX
 }
 
-__global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_ft_select_audit(DevView D, SelectArgs A, FTrackArgs F) {
+// the body of both select audits. COLS: the audited columns are the bits of `cols` (k_ft_masked_audit) instead of the
+// columns below n_audit
+template <bool COLS>
+__device__ __forceinline__ void ft_select_audit(const DevView &D, const SelectArgs &A, const FTrackArgs &F,
+                                                unsigned long long cols) {
   __shared__ double s_c[PMAF_SELECT_WAVES];
   __shared__ int s_v[PMAF_SELECT_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_ft_select_audit(DevV
   int viol = 0x7fffffff;
   if (k0 < k1) {
     const int j = lane;
-    const bool jv = j < n_audit;
+    const bool jv = COLS ? ((cols >> j) & 1ull) != 0 : j < n_audit;
     const int jc = j < n_obs ? j : 0;   // (the list's loads only; never a track column)
     V3 q = mk(o[jc], o[n_obs + jc], o[2 * (size_t)n_obs + jc]);
     // predictObstacles' v * dt, rounded once: the same double in every step of the chain
@@ -154,6 +162,23 @@ __global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_ft_select_audit(DevV
   }
 }
 
+__global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_ft_select_audit(DevView D, SelectArgs A, FTrackArgs F) {
+  ft_select_audit<false>(D, A, F, 0ull);
+}
+
+// the joint selection on a coupled handle (pmaf_select_pair_clear_tracked): the columns that ride on the OTHER member of
+// the pair are left to the pair side. The two populations' audited columns come by value; every other population of the
+// handle keeps the columns below n_audit. A mask is cut to the list (bits >= n_obs never count).
+__global__ __launch_bounds__(64 * PMAF_SELECT_WAVES) void k_ft_masked_audit(DevView D, SelectArgs A, FTrackArgs F, AuditColumns C) {
+  const int pop = blockIdx.y;
+  const int n_obs = D.n_obs < 64 ? D.n_obs : 64;
+  const unsigned long long list = n_obs >= 64 ? ~0ull : (1ull << n_obs) - 1ull;
+  const int n_audit = A.n_audit < n_obs ? (A.n_audit > 0 ? A.n_audit : 0) : n_obs;
+  unsigned long long cols = n_audit >= 64 ? ~0ull : (1ull << n_audit) - 1ull;
+  cols = pop == C.pop_a ? C.cols_a : (pop == C.pop_b ? C.cols_b : cols);
+  ft_select_audit<true>(D, A, F, cols & list);
+}
+
 __global__ __launch_bounds__(64) void k_audit_track_ft(int P, int n_obs, int cap, double dt, const double *obs /*[P][7][n_obs]*/,
                                                        FTrackArgs F, double *track /*[P][cap][3][n_obs]*/) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,6 +214,11 @@ __global__ __launch_bounds__(64) void k_audit_track_ft(int P, int n_obs, int cap
 
 void pmaf_k_launch_select_audit_ft(const DevView &D, const SelectArgs &A, const FTrackArgs &F, hipStream_t s) {
   hipLaunchKernelGGL(k_ft_select_audit, dim3((unsigned)D.N, (unsigned)D.P), dim3(64 * PMAF_SELECT_WAVES), 0, s, D, A, F);
+}
+
+void pmaf_k_launch_masked_audit_ft(const DevView &D, const SelectArgs &A, const FTrackArgs &F, const AuditColumns &cols,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(k_ft_masked_audit, dim3((unsigned)D.N, (unsigned)D.P), dim3(64 * PMAF_SELECT_WAVES), 0, s, D, A, F, cols);
 }
 
 void pmaf_k_launch_audit_track_ft(const DevView &D, const double *obs, const FTrackArgs &F, double *track, hipStream_t s) {

@@ -1,0 +1,42 @@
+// pmaf_xattach.hpp -- the cross audit on coupled handles (include/pmaf.h "joint selection on coupled handles":
+// pmaf_cross_audit_attached, pmaf_select_pair_clear_tracked): the structs and the launch interface between
+// pmaf_host_audit.cpp and the two kernels the calls add -- k_cross_audit_attached (pmaf_k_xattach.hip) and
+// k_ft_masked_audit (pmaf_k_auditft.hip). A header of its own so that no other kernel unit's inputs change with it:
+// CrossAuditArgs, SelectArgs and FTrackArgs stay what they are.
+#pragma once
+#include "pmaf_types.hpp"
+#include "pmaf_ftrack.hpp"
+
+// The terms of a pair beside the end effectors: the spheres of one population's list that ride on the OTHER population's
+// candidate path. All of it is the coupling's resident state (pmaf_fcouple.hpp: FCoupleArgs::src / scale / anchor, the
+// rows of the two populations) and the staged list's radii; nothing is uploaded for a call.
+//   term 0            x against y, R = separation
+//   term 1 + s        src_a[s] == pop_b: x against anchor_a[s] + scale_a[s] * y, R = radius + rad_a[s]
+//   term 1 + M + s    src_b[s] == pop_a: y against anchor_b[s] + scale_b[s] * x, R = radius + rad_b[s]
+struct XAttachSide {
+  const int32_t *src;       // [64] the population's row of FCoupleArgs::src, or NULL: nothing attached
+  const double *scale;      // [64]
+  const double *anchor;     // [3][64]
+  const double *rad;        // [M] the radii of the population's staged list (row 6 of its [7][n_obs] block)
+};
+struct CrossAuditAttachedArgs {
+  CrossAuditArgs X;         // the two sets, separation, clearance and step as in the cross audit
+  XAttachSide a, b;         // the lists of pop_a and of pop_b
+  int pop_a, pop_b, M;      // M = n_obs - 1 <= 60 while anything is attached
+  double radius;            // pmaf_params.radius
+  int32_t *sphere;          // [n_a][n_b] or NULL: the winning term's code
+};
+
+// pmaf_k_xattach.hip: k_cross_audit_attached on the cross audit's grid
+void pmaf_k_launch_cross_audit_attached(const CrossAuditAttachedArgs &A, hipStream_t s);
+
+// the obstacle side's audited columns of the joint selection's two populations: bit j set = obstacle j of the list is
+// audited. Every other population of the handle keeps columns 0 .. SelectArgs::n_audit - 1.
+struct AuditColumns {
+  int pop_a, pop_b;
+  unsigned long long cols_a, cols_b;
+};
+// pmaf_k_auditft.hip: k_ft_masked_audit on grid (N, P) -- k_ft_select_audit with the audited columns of two populations
+// given as masks. The list must already be staged. Needs D.n_obs <= 64.
+void pmaf_k_launch_masked_audit_ft(const DevView &D, const SelectArgs &A, const FTrackArgs &F, const AuditColumns &cols,
+                                   hipStream_t s);

@@ -88,6 +88,9 @@ SYMBOLS = {
     "pmaf_evaluate_paths_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, _dp, _ip, _ip, _ip, _dp]),
     "pmaf_select_clear_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp,
                                             _dp, _ip]),
+    "pmaf_cross_audit_attached": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, C.c_double, _dp, _ip, _ip]),
+    "pmaf_select_pair_clear_tracked": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32, C.c_double,
+                                                 C.c_double, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -888,6 +891,33 @@ class PmafPlanner:
                                                    _pi(out["rule"]), _pi(out["n_clear"]), _p(out["cost"]),
                                                    _p(out["clearance"]), _pi(out["first_violation"])))
         return {k: (v[0].item() if self.P == 1 else v) for k, v in out.items()}
+
+    # -- joint selection on coupled handles (include/pmaf.h "joint selection on coupled handles") --
+    def cross_audit_attached(self, pop_a, pop_b, obstacles, separation, step=False, sphere=False):
+        """cross_audit with the spheres of the handle's current coupling that ride on the other population's candidate
+        path as further terms of every pair (pmaf_cross_audit_attached); only the radii of `obstacles` are read.
+        clearance [N][N], followed by step and / or sphere (int32 [N][N]: 0 the end effectors, 1 + s a column of
+        pop_a's list, 1 + M + s one of pop_b's) where asked for"""
+        clr = np.zeros((self.N, self.N))
+        st = np.zeros((self.N, self.N), dtype=np.int32) if step else None
+        sp = np.zeros((self.N, self.N), dtype=np.int32) if sphere else None
+        self._chk(self.L.pmaf_cross_audit_attached(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)), float(separation),
+                                                   _p(clr), _pi(st), _pi(sp)))
+        out = (clr,) + ((st,) if step else ()) + ((sp,) if sphere else ())
+        return out if len(out) > 1 else clr
+
+    def select_pair_clear_tracked(self, pop_a, pop_b, obstacles, obstacle_margin, horizon, separation, pair_margin,
+                                  skip_trailing=False, prev_pair=None, adopt=False, first=None):
+        """select_pair_clear on a coupled / tracked handle (pmaf_select_pair_clear_tracked): the obstacle side is
+        select_clear_tracked's (tracks read from `first`) without the columns that ride on the other member of the pair,
+        the pair side is cross_audit_attached's on the windows; the same dict"""
+        o, args = self._joint_outputs()
+        pv = self._pair_arg(prev_pair)
+        self._chk(self.L.pmaf_select_pair_clear_tracked(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)),
+                                                        _pi(self._first(first)), float(obstacle_margin), int(horizon),
+                                                        1 if skip_trailing else 0, float(separation), float(pair_margin),
+                                                        _pi(pv), 1 if adopt else 0, *args))
+        return self._joint_dict(o)
 
     def launch_config(self):
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
