@@ -4,7 +4,8 @@
 # Translation units (compiled in parallel, objects kept in ../lib/obj):
 #   pmaf_k_w64.hip   x5  the wave-per-agent rollout kernel, once per arithmetic policy (-DPMAF_W64_MATH=0|1|2|3; the default
 #                        policy 2 in two units: one-slot / multi-slot kernels, -DPMAF_W64_PART=1|2; policy 3 = the opt-in
-#                        contracted one, the only units compiled with -ffp-contract=fast)
+#                        contracted one, the only units compiled with -ffp-contract=fast). The step (rollout_w64_body) and
+#                        its dispatch live in the header pmaf_rollout_w64_body.hpp, which the two track units include too
 #   pmaf_k_grp.hip   x3  the group rollout kernel (-DPMAF_GRP_MATH=0|2|3)
 #   pmaf_k_mw.hip    x3  the multi-wave-per-agent rollout kernel (62..256 obstacles at <= 1 wave per SIMD; -DPMAF_MW_MATH=1|2|3)
 #   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_xaudit_kernels.hpp) ... + the launch interface
@@ -13,13 +14,14 @@
 #                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
 #                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
 #   pmaf_k_select.hip    the selection against the live list (pmaf_select_clear / pmaf_adopt_best), a unit of its own for
-#                        the same reason; its object is select.o, outside the k_*.o set like slack.o
+#                        the same reason; its object is select.o, outside the k_*.o set like slack.o; k_select_audit is an
+#                        instance of pmaf_select_audit.hpp's one body, like the two audits of pmaf_k_auditft.hip
 #                        (tests/test_select_clear.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_pairclear.hip the joint selection (pmaf_select_pair_clear / pmaf_select_clear_tracks): the windowed lengths, the
 #                        joint reduction and its final block; a unit of its own for the same reason, object pairclear.o
 #                        (tests/test_pair_clear.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_track.hip     the repulsive track (include/pmaf.h): k_rollout_w64_track -- the one-slot wave-per-agent body of
-#                        pmaf_k_w64.hip instantiated with the tracked obstacle, compiled with the one-slot unit's flags --
+#                        pmaf_rollout_w64_body.hpp instantiated with the tracked obstacle, compiled with the one-slot unit's flags --
 #                        and k_track_from_best; a unit of its own for the same reason, object track.o
 #                        (tests/test_sentinel_track.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_ftrack.hip    the obstacle tracks (include/pmaf.h): k_rollout_w64_ftrack -- the same body instantiated with the
@@ -27,7 +29,8 @@
 #                        a unit of its own for the same reason, object ftrack.o
 #                        (tests/test_field_track.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_auditft.hip   the audits against the obstacle tracks (pmaf_select_clear_tracked / pmaf_evaluate_paths_tracked):
-#                        k_ft_select_audit and k_audit_track_ft, compiled with select.o's flags; a unit of its own for the
+#                        k_ft_select_audit, k_ft_masked_audit (pmaf_select_audit.hpp's body) and k_audit_track_ft (the chain of
+#                        pmaf_audit_chain.hpp), compiled with select.o's flags; a unit of its own for the
 #                        same reason, object auditft.o
 #                        (tests/test_tracked_audit.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_fcouple.hip   the obstacle tracks' device-side source (pmaf_couple_obstacle_tracks): k_fcouple_take and
@@ -87,10 +90,11 @@ KFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-m
 # PMAF_EXTRA_HFLAGS / PMAF_EXTRA_LDFLAGS: host objects / link line only (sanitizer builds: tools/asan.sh)
 HFLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -D__HIP_PLATFORM_AMD__ -I$ROCM/include ${PMAF_EXTRA_FLAGS} ${PMAF_EXTRA_HFLAGS}"
 
-DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
-DEPS_TRACK="pmaf_k_w64.hip pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
-DEPS_FTRACK="pmaf_k_w64.hip pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
-DEPS_AUDITFT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_auditft.hpp pmaf_xattach.hpp"   # ... and pmaf_k_auditft.hip
+DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_w64_body.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
+DEPS_TRACK="pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
+DEPS_FTRACK="pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
+DEPS_SELECT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_select_audit.hpp"   # ... and pmaf_k_select.hip
+DEPS_AUDITFT="$DEPS_SELECT pmaf_audit_chain.hpp pmaf_auditft.hpp pmaf_xattach.hpp"   # ... and pmaf_k_auditft.hip
 DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach.hip
 DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
@@ -107,6 +111,7 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   local extra=""
   [ "$src" = pmaf_k_track.hip ] && extra=$DEPS_TRACK
   [ "$src" = pmaf_k_ftrack.hip ] && extra=$DEPS_FTRACK
+  [ "$src" = pmaf_k_select.hip ] && extra=$DEPS_SELECT
   [ "$src" = pmaf_k_auditft.hip ] && extra=$DEPS_AUDITFT
   [ "$src" = pmaf_k_fcouple.hip ] && extra=$DEPS_FCOUPLE
   [ "$src" = pmaf_k_xattach.hip ] && extra=$DEPS_XATTACH

@@ -177,6 +177,40 @@ static void wait_select(pmaf_planner *h, const double *rec, int count, size_t re
       who, ": the selection kernel finished without publishing its result");
 }
 
+// The obstacle side of every selection, clear or joint: the caller's list into the pinned scratch, the SelectArgs fields
+// the audit reads, then k_select_stage and ONE audit in stream order -- k_select_audit; in a tracked call on a handle with
+// tracks k_ft_select_audit (no tracks attached: the untracked audit, whose result it is); and k_ft_masked_audit where
+// `ride` names columns of two populations' lists that the caller leaves to its pair side (bit j set = column j is NOT
+// audited here). Returns the arguments, which a caller with a pick completes. Behind select_scratch().
+static SelectArgs select_obstacle_side(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon,
+                                       bool skip_trailing, const TrackedCall *tracked, const AuditColumns *ride = nullptr) {
+  const DevView &D = h->D;
+  aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
+  SelectArgs A{};
+  A.obs_src = h->sel.dev();
+  A.obs = h->d_sel_obs;
+  A.margin = margin;
+  A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
+  A.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;   // (pmaf_select_clear: every obstacle counts, the trailing one included)
+  A.clr = h->d_sel_clr;
+  A.fv = h->d_sel_fv;
+  const bool ft = tracked && h->ftrk.on();
+  FTrackArgs F{};
+  if (ft) F = tracked_args(h, *tracked);
+  pmaf_k_launch_select_stage(D, A, h->stream);
+  if (!ft) {
+    pmaf_k_launch_select_audit(D, A, h->stream);
+  } else if (ride && (ride->cols_a | ride->cols_b) != 0) {
+    const uint64_t all = A.n_audit >= 64 ? ~(uint64_t)0 : ((uint64_t)1 << A.n_audit) - 1;
+    const AuditColumns audited{ride->pop_a, ride->pop_b, all & ~ride->cols_a, all & ~ride->cols_b};
+    pmaf_k_launch_select_audit_ft(D, A, F, &audited, h->stream);
+  } else {
+    pmaf_k_launch_select_audit_ft(D, A, F, nullptr, h->stream);
+  }
+  HIP_CHECK(hipGetLastError());
+  return A;
+}
+
 // One body behind pmaf_select_clear and pmaf_select_clear_tracked (tracked != NULL; n_audit = n_obs, or n_obs - 1 when
 // the tracked call skips the trailing obstacle). Called inside guarded().
 static void select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
@@ -197,28 +231,13 @@ static void select_clear(pmaf_planner *h, const double *obstacles, double margin
   const size_t list = (size_t)D.P * 7 * D.n_obs;
   double *rec = h->sel.host() + list;
   int32_t *prev_h = reinterpret_cast<int32_t *>(rec + (size_t)D.P * PMAF_SELECT_REC);
-  aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
   if (prev_idx) std::memcpy(prev_h, prev_idx, sizeof(int32_t) * (size_t)D.P);
-  SelectArgs A{};
-  A.obs_src = h->sel.dev();
-  A.obs = h->d_sel_obs;
-  A.margin = margin;
-  A.horizon = horizon < D.cap ? horizon : D.cap;   // (above the cap: the whole path)
-  A.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;   // (pmaf_select_clear: every obstacle counts, the trailing one included)
+  SelectArgs A = select_obstacle_side(h, obstacles, margin, horizon, skip_trailing, tracked);
   A.adopt = adopt ? 1 : 0;
   A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->sel.dev() + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
-  A.clr = h->d_sel_clr;
-  A.fv = h->d_sel_fv;
   A.result = h->sel.dev() + list;
   A.seq = (h->sel_seq += 1.0);
-  if (tracked && h->ftrk.on()) {   // (no tracks attached: the untracked audit, whose result it is)
-    const FTrackArgs F = tracked_args(h, *tracked);
-    pmaf_k_launch_select_stage(D, A, h->stream);
-    pmaf_k_launch_select_audit_ft(D, A, F, h->stream);
-    pmaf_k_launch_select_pick(D, A, h->stream);
-  } else {
-    pmaf_k_launch_select_clear(D, A, h->stream);
-  }
+  pmaf_k_launch_select_pick(D, A, h->stream);
   HIP_CHECK(hipGetLastError());
   wait_select(h, rec, D.P, PMAF_SELECT_REC, A.seq, who.c_str());
   if (adopt) h->has_best_h = 1;
@@ -638,32 +657,12 @@ static void select_pair_clear(pmaf_planner *h, int32_t pop_a, const PairClearSid
   sync(h);   // behind the running rollout, like the getters of its results
   select_scratch(h);
   // 1. the obstacle side of every population, as pmaf_select_clear runs it
-  aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
-  XAuditWindow win{horizon < D.cap ? horizon : D.cap};   // (above the cap: the whole path)
-  SelectArgs S{};
-  S.obs_src = h->sel.dev();
-  S.obs = h->d_sel_obs;
-  S.margin = obstacle_margin;
-  S.horizon = win.horizon;
-  S.n_audit = skip_trailing ? D.n_obs - 1 : D.n_obs;
-  S.clr = h->d_sel_clr;
-  S.fv = h->d_sel_fv;
   // (the tracked call: the columns of either list that ride on the OTHER member of the pair are the pair side's)
-  const uint64_t s_ab = tracked ? attached_columns(h, pop_a, sb.pop_b) : 0, s_ba = tracked ? attached_columns(h, sb.pop_b, pop_a) : 0;
-  const bool attached = (s_ab | s_ba) != 0;
-  if (tracked && h->ftrk.on()) {   // (no tracks and no coupling: the untracked audit, whose result it is)
-    const FTrackArgs F = tracked_args(h, *tracked);
-    pmaf_k_launch_select_stage(D, S, h->stream);
-    if (attached) {
-      const uint64_t all = S.n_audit >= 64 ? ~(uint64_t)0 : ((uint64_t)1 << S.n_audit) - 1;
-      pmaf_k_launch_masked_audit_ft(D, S, F, AuditColumns{pop_a, sb.pop_b, all & ~s_ab, all & ~s_ba}, h->stream);
-    } else {
-      pmaf_k_launch_select_audit_ft(D, S, F, h->stream);
-    }
-  } else {
-    pmaf_k_launch_select_audit(D, S, h->stream);
-  }
-  HIP_CHECK(hipGetLastError());
+  const AuditColumns ride{pop_a, sb.pop_b, tracked ? attached_columns(h, pop_a, sb.pop_b) : 0,
+                          tracked ? attached_columns(h, sb.pop_b, pop_a) : 0};
+  const bool attached = (ride.cols_a | ride.cols_b) != 0;
+  const SelectArgs S = select_obstacle_side(h, obstacles, obstacle_margin, horizon, skip_trailing != 0, tracked, &ride);
+  XAuditWindow win{S.horizon};
   const XAuditAttach att{pop_a, sb.pop_b, h->d_sel_obs, false};
   // 2., 3. the windowed lengths and the cross audit on them; the matrix stays in the scratch
   const bool want = out.pair_steps != nullptr;

@@ -3,7 +3,7 @@
 // and whose trailing repulsive obstacle may follow a repulsive track as in k_rollout_w64_track. A translation unit and an
 // object of its own (ftrack.o): the other units' code objects do not move with it.
 //
-// The step is rollout_w64_body of pmaf_k_w64.hip, instantiated here -- and only here -- with FTRACK = true (and TRACK =
+// The step is rollout_w64_body of pmaf_rollout_w64_body.hpp, instantiated here -- and only here -- with FTRACK = true (and TRACK =
 // true: one kernel serves field tracks, a repulsive track, or both, with empty lane masks for whatever is absent). What
 // FTRACK adds to the loop: six 8-byte loads per lane at the top of the step, for the step after it -- lane i reads
 // obstacle i's column of the point, the rows contiguous across the lanes -- and six selects behind the tail's
@@ -13,29 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#define PMAF_W64_BODY_ONLY 1
-#include "pmaf_k_w64.hip"
+#include "pmaf_rollout_w64_body.hpp"
 #include "pmaf_ftrack.hpp"
 
 using namespace pmaf;
 
 static_assert(PMAF_FTRACK_LANES == 64 && PMAF_FTRACK_POINT == 384, "rollout_w64_body's FTRACK loads assume [6][64] doubles per point");
-
-// track_reachable of pmaf_k_track.hip (that unit is not a header): can ANY point of the repulsive track the rollout may
-// read come into repelForce's range? Conservative only: the loop it selects computes the same bits either way.
-__device__ __forceinline__ bool ftrack_sentinel_track_reachable(int lane, V3 p0, const double *trk, int n_pts, double zsent_lt,
-                                                                const PopConst &C, int steps) {
-  const double adt = fabs(C.dt);
-  const double per_step = 6.5 * adt * adt + fabs(C.vel_max) * adt;
-  const double reach = (double)steps * per_step * 1.001 + 1e-9;
-  const double range = __builtin_sqrt(zsent_lt) * 1.001;
-  bool any = false;
-  for (int j = lane; j < n_pts; j += 64) {
-    const V3 y = mk(trk[3 * j], trk[3 * j + 1], trk[3 * j + 2]);
-    any = any || !(norm(p0 - y) > range + reach);   // NaN anywhere: keep testing
-  }
-  return wave_any(any);
-}
 
 template <bool DPPSUM, bool PLAIN>
 __global__ __launch_bounds__(64) void k_rollout_w64_ftrack(DevView D, CostParams CP, TrackArgs T, FTrackArgs F) {
@@ -53,7 +36,7 @@ __global__ __launch_bounds__(64) void k_rollout_w64_ftrack(DevView D, CostParams
   PMAF_BOUND(L >= 0 && L <= T.max_len);
   bool reach;
   if (L > 0) {
-    reach = ftrack_sentinel_track_reachable(lane, p0, trk, (L < D.cap) ? L : D.cap, D.zsent_lt[pop], C0, D.cap);
+    reach = track_reachable(lane, p0, trk, (L < D.cap) ? L : D.cap, D.zsent_lt[pop], C0, D.cap);
   } else {
     const V3 sp = mk(src[M], src[n_obs + M], src[2 * n_obs + M]);
     const V3 sv = mk(src[3 * n_obs + M], src[4 * n_obs + M], src[5 * n_obs + M]);
@@ -67,15 +50,7 @@ __global__ __launch_bounds__(64) void k_rollout_w64_ftrack(DevView D, CostParams
 #define PMAF_BODY(T_) \
   if (!reach) rollout_w64_body<1, T_, MATH, 0, DPPSUM, PLAIN, false, false, true, true>(D, CP, lane, pop, a, trk, L, ftrk, FL, first); \
   else rollout_w64_body<1, T_, MATH, 1, DPPSUM, PLAIN, false, false, true, true>(D, CP, lane, pop, a, trk, L, ftrk, FL, first)
-  switch (D.types[a]) {
-    case T_GOAL: PMAF_BODY(T_GOAL); break;
-    case T_OBST: PMAF_BODY(T_OBST); break;
-    case T_GOALOBST: PMAF_BODY(T_GOALOBST); break;
-    case T_VEL: PMAF_BODY(T_VEL); break;
-    case T_RANDOM: PMAF_BODY(T_RANDOM); break;
-    case T_HAD: PMAF_BODY(T_HAD); break;
-    default: break;
-  }
+  PMAF_W64_EACH_TYPE(D.types[a], PMAF_BODY)
 #undef PMAF_BODY
 }
 

@@ -277,7 +277,7 @@ __device__ __forceinline__ void circ_and_scale_mw(const int lane, const int w, c
   scale = (sqn(F) >= C.zf_gt) ? sc : scale;  // norm(F) > 1e-5
 }
 
-// the step loop: rollout_w64_body's one-slot (PRE) loop on W waves (pmaf_k_w64.hip has the commentary of every block)
+// the step loop: rollout_w64_body's one-slot (PRE) loop on W waves (pmaf_rollout_w64_body.hpp has the commentary of every block)
 template <int W, int TYPE, int MATH, int SENT, bool PLAIN, bool PRE>
 __device__ __forceinline__ void rollout_mw_body(const DevView &D, const CostParams &CP, const int lane, const int w,
                                                 const int pop, const int a, const int per) {

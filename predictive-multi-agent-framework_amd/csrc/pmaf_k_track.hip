@@ -3,39 +3,18 @@
 // k_track_from_best, which copies a population's selected path into another population's track. A translation unit
 // and an object of its own: the other units' code objects do not move with it.
 //
-// The step is rollout_w64_body of pmaf_k_w64.hip, instantiated here -- and only here -- with TRACK = true (that file
-// is included for the body alone; its launcher and kernels are not compiled into this object). What TRACK adds to the
-// loop that carries code for the repulsive obstacle (SENT == 1, the obstacle in lane 60): one 24-byte load from a
-// wave-uniform address at the top of the step, for the step after it, and three selects behind the tail's
-// O.p += O.v dt that put the point into lane 60. The loop without code for the obstacle (SENT == 0) is the same
-// instantiation as in k_rollout_w64.
+// The step is rollout_w64_body of pmaf_rollout_w64_body.hpp, instantiated here -- and only here -- with TRACK = true.
+// What TRACK adds to the loop that carries code for the repulsive obstacle (SENT == 1, the obstacle in lane 60): one
+// 24-byte load from a wave-uniform address at the top of the step, for the step after it, and three selects behind the
+// tail's O.p += O.v dt that put the point into lane 60. The loop without code for the obstacle (SENT == 0) is the same
+// instantiation as in k_rollout_w64. track_reachable, which decides between the two for a track, is in that header too.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#define PMAF_W64_BODY_ONLY 1
-#include "pmaf_k_w64.hip"
+#include "pmaf_rollout_w64_body.hpp"
 #include "pmaf_track.hpp"
 
 using namespace pmaf;
-
-// sentinel_reachable (pmaf_rollout_w64.hpp) for a track: can ANY point the rollout may read -- y_0 ... y_{min(L, cap) - 1},
-// the held last one included -- come into repelForce's range? The agent is never farther than steps * per_step from its
-// start (|a| <= 13, |v| <= vel_max, both clamped), whatever step a point belongs to, so a point farther than
-// range + reach from the start is out of range at every step. Same margins as sentinel_reachable; lanes stride over the
-// points. Conservative only: the loop it selects computes the same bits either way.
-__device__ __forceinline__ bool track_reachable(int lane, V3 p0, const double *trk, int n_pts, double zsent_lt,
-                                                const PopConst &C, int steps) {
-  const double adt = fabs(C.dt);
-  const double per_step = 6.5 * adt * adt + fabs(C.vel_max) * adt;
-  const double reach = (double)steps * per_step * 1.001 + 1e-9;
-  const double range = __builtin_sqrt(zsent_lt) * 1.001;
-  bool any = false;
-  for (int j = lane; j < n_pts; j += 64) {
-    const V3 y = mk(trk[3 * j], trk[3 * j + 1], trk[3 * j + 2]);
-    any = any || !(norm(p0 - y) > range + reach);   // NaN anywhere: keep testing
-  }
-  return wave_any(any);
-}
 
 template <bool DPPSUM, bool PLAIN>
 __global__ __launch_bounds__(64) void k_rollout_w64_track(DevView D, CostParams CP, TrackArgs T) {
@@ -68,15 +47,7 @@ __global__ __launch_bounds__(64) void k_rollout_w64_track(DevView D, CostParams 
     else rollout_w64_body<1, T_, MATH, 1, DPPSUM, PLAIN, true, false, true>(D, CP, lane, pop, a, trk, L); \
   } else if (!reach) rollout_w64_body<1, T_, MATH, 0, DPPSUM, PLAIN, false, false>(D, CP, lane, pop, a); \
   else rollout_w64_body<1, T_, MATH, 1, DPPSUM, PLAIN, false, false, true>(D, CP, lane, pop, a, trk, L)
-  switch (D.types[a]) {
-    case T_GOAL: PMAF_BODY(T_GOAL); break;
-    case T_OBST: PMAF_BODY(T_OBST); break;
-    case T_GOALOBST: PMAF_BODY(T_GOALOBST); break;
-    case T_VEL: PMAF_BODY(T_VEL); break;
-    case T_RANDOM: PMAF_BODY(T_RANDOM); break;
-    case T_HAD: PMAF_BODY(T_HAD); break;
-    default: break;
-  }
+  PMAF_W64_EACH_TYPE(D.types[a], PMAF_BODY)
 #undef PMAF_BODY
 }
 

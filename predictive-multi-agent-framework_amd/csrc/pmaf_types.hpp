@@ -327,10 +327,13 @@ void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s);
 void pmaf_k_launch_cross_audit_slack(const CrossAuditSlackArgs &A, hipStream_t s);
 // the two stages of the pair reduction back to back
 void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s);
-// pmaf_k_select.hip: k_select_stage, k_select_audit (grid (N, P)) and k_select_pick (grid P) in stream order
-void pmaf_k_launch_select_clear(const DevView &D, const SelectArgs &A, hipStream_t s);
-// the first two of them alone: the per-agent clearance and first violation into A.clr / A.fv, no pick
+// pmaf_k_select.hip, one launcher per kernel; a selection enqueues stage, an audit and the pick in stream order:
+// k_select_stage (the list A.obs_src into A.obs), k_select_audit on grid (N, P) (the per-agent clearance and first
+// violation into A.clr / A.fv; a tracked handle launches pmaf_auditft.hpp's audit in its place) and k_select_pick on
+// grid P (the rule, the record, the adopt stores)
+void pmaf_k_launch_select_stage(const DevView &D, const SelectArgs &A, hipStream_t s);
 void pmaf_k_launch_select_audit(const DevView &D, const SelectArgs &A, hipStream_t s);
+void pmaf_k_launch_select_pick(const DevView &D, const SelectArgs &A, hipStream_t s);
 // pmaf_k_pairclear.hip: k_pairclear_window; k_pairclear_reduce and k_pairclear_final back to back
 void pmaf_k_launch_pairclear_window(const PairWindowArgs &A, hipStream_t s);
 void pmaf_k_launch_pairclear(const DevView &D, const PairClearArgs &A, hipStream_t s);

@@ -31,12 +31,9 @@ struct CrossAuditAttachedArgs {
 void pmaf_k_launch_cross_audit_attached(const CrossAuditAttachedArgs &A, hipStream_t s);
 
 // the obstacle side's audited columns of the joint selection's two populations: bit j set = obstacle j of the list is
-// audited. Every other population of the handle keeps columns 0 .. SelectArgs::n_audit - 1.
+// audited. Every other population of the handle keeps columns 0 .. SelectArgs::n_audit - 1. Handed to the tracked audit's
+// launcher (pmaf_k_launch_select_audit_ft, pmaf_auditft.hpp), which then runs k_ft_masked_audit.
 struct AuditColumns {
   int pop_a, pop_b;
   unsigned long long cols_a, cols_b;
 };
-// pmaf_k_auditft.hip: k_ft_masked_audit on grid (N, P) -- k_ft_select_audit with the audited columns of two populations
-// given as masks. The list must already be staged. Needs D.n_obs <= 64.
-void pmaf_k_launch_masked_audit_ft(const DevView &D, const SelectArgs &A, const FTrackArgs &F, const AuditColumns &cols,
-                                   hipStream_t s);

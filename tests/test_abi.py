@@ -70,6 +70,22 @@ def test_product_sources_do_not_reference_the_oracle():
                             raise AssertionError("%s references the oracle: %s" % (f, line.strip()))
 
 
+def test_kernel_units_share_code_through_headers_only():
+    """a .hip file is a translation unit, never an include: what units share lives in a header (the rollout step in
+    csrc/pmaf_rollout_w64_body.hpp), and the fence macro that once let two units include pmaf_k_w64.hip is gone"""
+    csrc = os.path.join(conftest.ROOT, "predictive-multi-agent-framework_amd", "csrc")
+    for base in (csrc, os.path.join(conftest.ROOT, "tools")):
+        for dp, _, files in os.walk(base):
+            for f in files:
+                if not f.endswith((".py", ".hpp", ".h", ".hip", ".cpp", ".sh", ".md")):
+                    continue
+                txt = open(os.path.join(dp, f), errors="ignore").read()
+                assert "PMAF_W64_BODY_ONLY" not in txt, f
+                if base == csrc:
+                    m = re.search(r"#\s*include\s*[\"<][^\">]*\.hip[\">]", txt)
+                    assert m is None, "%s includes a translation unit: %s" % (f, m.group(0) if m else "")
+
+
 def test_throughput_kernels_keep_two_waves_per_simd(pmaf):
     """k_rollout_grp hides its latencies with a second wave on the SIMD, i.e. it
     must stay within 256 VGPRs (it sits just below; csrc/build.sh records every

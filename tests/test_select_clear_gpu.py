@@ -113,6 +113,23 @@ def test_shapes_horizons_margins(pmaf, scenes, hip_lib, shape):
     assert seen
 
 
+@pytest.mark.parametrize("horizon", [1, 2, 3, 5])
+def test_windows_shorter_than_two_points_per_wave(pmaf, scenes, hip_lib, horizon):
+    """the audit splits the window of w = min(n, horizon) points over four waves in quarters of ceil(w / 4): w = 1, 2, 3
+    leave waves without a step (k0 == k1), w = 5 gives quarters of 2, 2, 1, 0 -- at P = 2, N = 5, M = 3, 9 points"""
+    pl, scs, start = rollout_case(pmaf, scenes, 2, 5, 3, 8)
+    try:
+        _evaluate(pl, scs[0])
+        live = live_list(scenes, start)
+        tables, audits = _handle_tables(pl), {}
+        assert all(n >= 5 for row in tables[1] for n in row)      # w = horizon for every agent
+        for margin in MARGINS:
+            got = check_select(pl, scs[0], live, margin, horizon, hip_lib, [1, 3], tables, "short window", audits)
+            assert (got["first_violation"] <= horizon).all()
+    finally:
+        pl.close()
+
+
 def test_every_rule_and_every_n_clear_regime_occurred(pmaf, scenes, hip_lib):
     seen = set()
     for shape in SHAPES:

@@ -341,6 +341,29 @@ def test_lengths_offsets_windows_rules(pmaf, scenes, hip_lib, shape):
         c.close()
 
 
+@pytest.mark.parametrize("horizon", [1, 2, 3, 5])
+def test_windows_shorter_than_two_points_per_wave(pmaf, scenes, hip_lib, horizon):
+    """the audit splits the window of w = min(n, horizon) points over four waves in quarters of ceil(w / 4): w = 1, 2, 3
+    leave waves without a step, w = 5 gives quarters of 2, 2, 1, 0 -- at P = 2, N = 5, M = 3, cap = 9, on tracks read
+    from their start, from the middle, and from an offset at or past the last point (every step holds it); and on the
+    same handle without tracks, where the tracked call runs the untracked kernel"""
+    c = Case(pmaf, scenes, hip_lib, 2, 5, 3, 9)
+    try:
+        assert all(n >= 5 for row in c.n for n in row)      # w = horizon for every agent
+        for margin in (0.0, 0.1):
+            c.check_select(margin, horizon, prev=[1, 3], what="no tracks")
+        for name, first in (("Lcap", 0), ("short", 1), ("Lcap", "L-1"), ("short", "L+3"), ("L2", INT32_MAX)):
+            t = _tracks(c, name)
+            c.attach(t)
+            f = [fref.resolve_first(first, len(t[p])) for p in range(c.P)]
+            for margin in (0.0, 0.1):
+                for skip in (False, True):
+                    got = c.check_select(margin, horizon, first=f, skip=skip, prev=[1, 3], what=name)
+                    assert (got["first_violation"] <= horizon).all()
+    finally:
+        c.close()
+
+
 def test_a_tie_between_a_tracked_and_the_trailing_obstacle_goes_to_the_smaller_index(pmaf, scenes, hip_lib):
     c = Case(pmaf, scenes, hip_lib, 1, 5, 3, 70)
     try:
