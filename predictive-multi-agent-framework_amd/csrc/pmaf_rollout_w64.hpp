@@ -571,10 +571,14 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   // compaction stores (a wave's DS instructions execute in order), its LDS round trip runs under that chain instead
   // of in front of the sum, where the disassembly showed ds_read / s_waitcnt lgkmcnt(0) back to back. (An empty list
   // reads the all-zero padding chunk: the sum below needs no `count > 0` test for it.)
-  double e_first = 0.0;
+  // One slot per lane: the SECOND chunk is fetched here as well, whatever the count (the multi-slot sum below reads that
+  // address unconditionally too: it lies inside the list area, and a stale chunk is never added when count <= 16), so
+  // that a list of more than 16 terms finds it in registers behind the scaling chain instead of waiting for it there.
+  double e_first = 0.0, e_second = 0.0;
   if (DPPSUM) {
     wave_lds_fence();
     e_first = clist[lane];
+    if (TILES == 1) e_second = clist[(16 << 2) + lane];
   }
 
   // ---- attractorForceScaling value (:212-226), branchless ----
@@ -654,8 +658,8 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
     // write of EXEC or of the DPP source ahead of a DPP instruction needs 5 / 2 wait states -> s_nop 4 in front; the
     // block's result is next read by v_readlane / the following block (s_nop 1 behind it covers a DPP reader).
     // Measured (one box): C3 1248.7 -> 1230.9 us, 200 / 256 obstacles 1270 -> 1197 / 1382 -> 1297 us per launch; the
-    // one-slot kernel gains nothing (C2 279.1 vs 279.2 us: the block cannot be interleaved with the scaling chain) and
-    // keeps the compiler-visible builtin form.
+    // one-slot kernel gained nothing from the block form for its FIRST chunk (C2 279.1 vs 279.2 us: the block cannot be
+    // interleaved with the scaling chain): its first chunk is separate statements, its further chunks this block (below).
     // Round 3: the next chunk's ds_read is in flight while this chunk is added (one register pair more).
     double one = 1.0;
     asm volatile("" : "+v"(one));
@@ -691,9 +695,8 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
       e = en;
     }
     } else {
-#define PMAF_BC(K) acc = acc + __builtin_amdgcn_update_dpp(e, e, 0x150 + K, 0xf, 0xf, true);
-#define PMAF_BC16 PMAF_BC(0) PMAF_BC(1) PMAF_BC(2) PMAF_BC(3) PMAF_BC(4) PMAF_BC(5) PMAF_BC(6) PMAF_BC(7) \
-                  PMAF_BC(8) PMAF_BC(9) PMAF_BC(10) PMAF_BC(11) PMAF_BC(12) PMAF_BC(13) PMAF_BC(14) PMAF_BC(15)
+      double one = 1.0;
+      asm volatile("" : "+v"(one));
       // the first chunk unconditionally, in the block of the scaling chain (its 16 dependent adds interleave with that
       // chain's instructions; no branch, no loop for the common list of <= 16 terms); longer lists continue in a loop
       {
@@ -703,8 +706,6 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
         // source e comes out of the ds_read, not out of a VALU instruction (2 wait states otherwise; the s_nop in front
         // of the first one covers a copy the register allocator might place there), EXEC is only written by SALU
         // instructions on this path (a VALU write would need 5).
-        double one = 1.0;
-        asm volatile("" : "+v"(one));
         double e = e_first;
         asm volatile("s_nop 1" : "+v"(e));
 #define PMAF_FM1(K) asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(e), "v"(one));
@@ -715,12 +716,22 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
       // (keeps the rest of the scaling chain in THIS block, in front of the rare loop: left alone the compiler sinks
       // it behind the loop, where it can no longer interleave with the 16 dependent adds)
       if (PMAF_SUM_TAIL_PIN) asm volatile("" : : "v"(sc), "v"(acc));
+      // Longer lists (C2 late in its episode: up to 25 terms, on 40 % of the bounding agent's steps) in the form of the
+      // multi-slot sum above: one asm block of sixteen fused accumulates per chunk (s_nop 4 in front, s_nop 1 behind), the
+      // second chunk out of the registers it was fetched into in front of the scaling chain, every further chunk's
+      // ds_read in flight while its predecessor is added (behind the last chunk: padding / scratch, never used).
+      double e = e_second;
       for (int c16 = 16; PMAF_RARE(c16 < count); c16 += 16) {
-        const double e = clist[(c16 << 2) + lane];
-        PMAF_BC16
+        const double en = clist[((c16 + 16) << 2) + lane];
+#define PMAF_FM(K) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
+        asm volatile("s_nop 4\n\t"
+                     PMAF_FM(0) PMAF_FM(1) PMAF_FM(2) PMAF_FM(3) PMAF_FM(4) PMAF_FM(5) PMAF_FM(6) PMAF_FM(7)
+                     PMAF_FM(8) PMAF_FM(9) PMAF_FM(10) PMAF_FM(11) PMAF_FM(12) PMAF_FM(13) PMAF_FM(14) PMAF_FM(15)
+                     "s_nop 1"
+                     : "+v"(acc) : "v"(e), "v"(one));
+#undef PMAF_FM
+        e = en;
       }
-#undef PMAF_BC16
-#undef PMAF_BC
     }
     F = mk(readlane_d(acc, 0), readlane_d(acc, 16), readlane_d(acc, 32));
   }
