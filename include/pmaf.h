@@ -738,9 +738,8 @@ int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const in
  *     windows, held to pair_margin.
  * On a handle without tracks and without coupling the call is pmaf_select_pair_clear(late = NULL) bit for bit, through
  * the same kernels.
- * Limits that remain: no `late` (the slack band sees the end effectors only); pmaf_select_clear_tracks, whose side B
- * comes from the caller, sees neither tracks nor attachments; the C++ facade (one population per handle) uses neither
- * call. */
+ * Limits that remain: pmaf_select_clear_tracks, whose side B comes from the caller, sees neither tracks nor
+ * attachments; the C++ facade (one population per handle) uses neither call. Timing slack: the block below. */
 int pmaf_cross_audit_attached(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
                               double *clearance, int32_t *step, int32_t *sphere);
 int pmaf_select_pair_clear_tracked(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles,
@@ -749,6 +748,59 @@ int pmaf_select_pair_clear_tracked(pmaf_planner *h, int32_t pop_a, int32_t pop_b
                                    int32_t *pair, int32_t *rule, int32_t *n_feasible, int32_t *n_clear, double *pair_cost,
                                    double *pair_clearance, double *obstacle_clearance, int32_t *first_violation,
                                    double *worst_excess, int32_t *pair_steps);
+
+/* ---- joint selection on coupled handles with timing slack: late arms held to the riding spheres (exports added under
+ * ABI 7) ----
+ * The slacked calls (pmaf_cross_audit_slack, pmaf_select_pair_slack, pmaf_select_pair_clear(late)) admit every pair of
+ * steps in a band but see the two end effectors only; the attached calls above hold a pair to the riding spheres, step
+ * against step only. These two calls are their product: every term of a pair over the whole band. No reference
+ * equivalent.
+ * Carried over unchanged: the terms, their order, S_ab / S_ba, the ride z = RN(anchor + RN(scale * p)), R_0 =
+ * separation, R = RN(radius + r) with r from the caller's list and the codes 0, 1 + s, 1 + M + s are
+ * pmaf_cross_audit_attached's; xh, yh, K = max(n, m), the hold rule and the empty-path rule are pmaf_cross_audit's; the
+ * admitted set is pmaf_cross_audit_slack's: (k, l) in [0, K)^2 with -late_b <= l - k <= late_a. k is ALWAYS A's step
+ * and l ALWAYS B's.
+ *   term 0:                  u = xh_k, z = yh_l
+ *   term 1 + s, s in S_ab:   u = xh_k, z = RN(anchor[a][s] + RN(scale[a][s] * yh_l)): the sphere is a part of arm B and
+ *                            is on arm B's clock
+ *   term 1 + M + s, S_ba:    u = yh_l, z = RN(anchor[b][s] + RN(scale[b][s] * xh_k))
+ *   d2_t   = the least dot(u - z, u - z) over the admitted pairs under the total order (d2, k, l): a scan with k, then l
+ *            ascending and a strict `<` from +infinity; a NaN never wins
+ *   gap_t  = sqrt(d2_t) - R_t
+ *   clearance(i,j) = min over t of gap_t, strict `<` in term order: ties go to the smallest term, then to that term's
+ *            least (k, l). (step_a, step_b)(i,j) and sphere(i,j) are the winning term's. Nothing won, or an empty
+ *            path: +infinity / -1 / -1 / -1.
+ * Consequences:
+ *   - late_a = late_b = 0 gives pmaf_cross_audit_attached's clearance and sphere bit for bit, with step_a = step_b =
+ *     step (through this call's own kernel all the same);
+ *   - with S_ab and S_ba empty the call is pmaf_cross_audit_slack bit for bit, and sphere is 0 wherever a step won;
+ *   - the clearance never grows with either slack;
+ *   - audit(A, B, late_a, late_b) has the transposed clearance bits of audit(B, A, late_b, late_a): each sphere's u - z is
+ *     the same vector in both calls, the codes swap 1 + s <-> 1 + M + s, and the steps transpose only where the minimum
+ *     is unique (the tie order (d2, k, l) is not symmetric).
+ *
+ * pmaf_cross_audit_attached_slack: the matrices above on the whole CURRENT paths of pop_a and pop_b. clearance [N][N] is
+ * required; step_a, step_b and sphere [N][N] may each be NULL. A negative slack: PMAF_ERR_INVALID; a slack of
+ * max_prediction_steps or more already admits every pair of steps and is clamped on the host. Waits, state rules (none
+ * is changed) and every other validation are pmaf_cross_audit_attached's.
+ *
+ * pmaf_select_pair_clear_tracked_slack: late == NULL is pmaf_select_pair_clear_tracked exactly, through the same
+ * kernels. With late [2] = (late_a, late_b): the obstacle side is unchanged; the pair side is the matrix above on the
+ * two path sets cut to their windows, held to pair_margin; pair_steps = (step_a, step_b) of the returned pair. Rules
+ * -1 / 0 / 1 / 2, S, g, record, adoption, waits, the abandoned-tick refusal, outputs and which of them may be NULL are
+ * untouched. Where nothing rides on the other member of the pair the pair side is pmaf_select_pair_clear(late)'s.
+ * Limits that remain: pmaf_select_clear_tracks sees neither tracks nor attachments; the C++ facade (one population per
+ * handle) and the planner node use none of this. */
+int pmaf_cross_audit_attached_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles,
+                                    double separation, int32_t late_a, int32_t late_b, double *clearance,
+                                    int32_t *step_a, int32_t *step_b, int32_t *sphere);
+int pmaf_select_pair_clear_tracked_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles,
+                                         const int32_t *first, double obstacle_margin, int32_t horizon,
+                                         int32_t skip_trailing, double separation, double pair_margin,
+                                         const int32_t *late /* [2] or NULL */, const int32_t *prev_pair, int32_t adopt,
+                                         int32_t *pair, int32_t *rule, int32_t *n_feasible, int32_t *n_clear,
+                                         double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                                         int32_t *first_violation, double *worst_excess, int32_t *pair_steps);
 
 /* CfManager::getLinkForce -> CfAgent::bodyForce, B/src/cf_manager.cpp:169-182,
  * B/src/cf_agent.cpp:229-234: repel-only force of population `pop`'s last

@@ -1,7 +1,7 @@
-// pmaf_cross_audit.hpp -- the cross audit's tile, what its three kernels share: k_cross_audit (pmaf_xaudit_kernels.hpp,
-// compiled in pmaf_k_misc.hip), k_cross_audit_slack (pmaf_k_slack.hip) and k_cross_audit_attached (pmaf_k_xattach.hip).
-// All own the same tile and differ only in the steps of B a step of A is held against and in what is staged of a point
-// (the attached audit: the sphere that rides on it); this header has the tile's shape (the constants the GPU tests read their
+// pmaf_cross_audit.hpp -- the cross audit's tile, what its four kernels share: k_cross_audit (pmaf_xaudit_kernels.hpp,
+// compiled in pmaf_k_misc.hip), k_cross_audit_slack (pmaf_k_slack.hip), k_cross_audit_attached (pmaf_k_xattach.hip) and
+// k_xaudit_attached_slack (pmaf_k_xattach_slack.hip). All own the same tile and differ only in the steps of B a step
+// of A is held against and in what is staged of a point (the attached audits: the sphere that rides on it); this header has the tile's shape (the constants the GPU tests read their
 // shapes from), its staging into LDS, its prologue and the store of one finished pair. No kernel is defined here.
 //
 // Tile          a block of 256 threads owns T = 32 paths of A x T = 32 paths of B and walks the steps in chunks of

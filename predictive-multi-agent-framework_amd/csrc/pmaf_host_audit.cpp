@@ -304,7 +304,7 @@ struct XAuditSlack {
 // Device scratch of one call: clearance [n_a][n_b] | partials | result | tracks [n_tracks][cap][3] | step [n_a][n_b] |
 // track lengths [n_tracks] | the slacked calls' second step matrix [n_a][n_b] | the joint selection's parts: partials |
 // track costs [n_tracks] | windowed lengths [n_a], [n_b] (doubles first, the int32 parts padded: every part stays 8-byte
-// aligned)
+// aligned) | the slacked attached audit's sphere matrix [n_a][n_b] (LAST: no other call's layout moves with it)
 struct XAuditBuf {
   double *clearance;
   PairBest *partial;
@@ -316,13 +316,15 @@ struct XAuditBuf {
   PairClearBest *pc_partial;
   double *track_cost;
   int32_t *win_a, *win_b;
+  int32_t *sphere;   // (the slacked attached audit only: the attached audit keeps its sphere matrix where step_b lies)
 };
 // the joint selection's audit window: the cross audit then runs on the lengths min(n, horizon) (k_pairclear_window), its
 // matrix stays in the scratch, and nothing is copied out
 struct XAuditWindow {
   int32_t horizon;   // 1 .. cap
 };
-static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps, bool joint = false) {
+static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t n_tracks, bool two_steps, bool joint = false,
+                                bool third = false) {
   const size_t pairs = n_a * n_b;
   if (pairs >= 0x7fffffffull) fail(PMAF_ERR_INVALID, "cross audit: the number of pairs must stay below 2^31");
   const size_t b_clr = sizeof(double) * pairs, b_part = sizeof(PairBest) * PMAF_XAUDIT_PARTIALS, b_res = sizeof(PairResult);
@@ -331,7 +333,7 @@ static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t 
   const size_t b_pc = sizeof(PairClearBest) * PMAF_XAUDIT_PARTIALS, b_tc = sizeof(double) * n_tracks;
   const size_t b_wa = (sizeof(int32_t) * n_a + 7) & ~(size_t)7, b_wb = (sizeof(int32_t) * n_b + 7) & ~(size_t)7;
   const size_t total = b_clr + b_part + b_res + b_trk + b_step + b_len + (two_steps ? b_step : 0) +
-                       (joint ? b_pc + b_tc + b_wa + b_wb : 0);
+                       (joint ? b_pc + b_tc + b_wa + b_wb : 0) + (third ? b_step : 0);
   h->d_xaudit.reserve(total);
   XAuditBuf B;
   char *p = h->d_xaudit.get();
@@ -346,7 +348,8 @@ static XAuditBuf xaudit_scratch(pmaf_planner *h, size_t n_a, size_t n_b, size_t 
   B.pc_partial = joint ? reinterpret_cast<PairClearBest *>(p) : nullptr; p += joint ? b_pc : 0;
   B.track_cost = joint ? reinterpret_cast<double *>(p) : nullptr; p += joint ? b_tc : 0;
   B.win_a = joint ? reinterpret_cast<int32_t *>(p) : nullptr; p += joint ? b_wa : 0;
-  B.win_b = joint ? reinterpret_cast<int32_t *>(p) : nullptr;
+  B.win_b = joint ? reinterpret_cast<int32_t *>(p) : nullptr; p += joint ? b_wb : 0;
+  B.sphere = third ? reinterpret_cast<int32_t *>(p) : nullptr;
   return B;
 }
 
@@ -363,7 +366,9 @@ static void clamp_slack(const pmaf_planner *h, XAuditSlack *slack, const char *w
 // the attached audit (include/pmaf.h "joint selection on coupled handles"): the two populations whose lists' spheres
 // ride on each other's candidate paths, and the staged list [P][7][n_obs] on the device whose radii the terms take. The
 // terms themselves are the coupling's resident rows (pmaf_planner::FieldTrack::d_src / d_scale / d_anchor): nothing is
-// uploaded for the call. The sphere matrix, when wanted, lies where the slacked calls keep their second step matrix.
+// uploaded for the call. The sphere matrix, when wanted, lies where the slacked calls keep their second step matrix; a call
+// with a slack AND an attachment (pmaf_cross_audit_attached_slack, the pair side of pmaf_select_pair_clear_tracked_slack)
+// wants both, and its sphere matrix is XAuditBuf::sphere, the last part of the scratch.
 struct XAuditAttach {
   int32_t pop_a, pop_b;
   const double *list;
@@ -387,7 +392,8 @@ static XAttachSide attach_side(const pmaf_planner *h, const XAuditAttach &T, int
                      f.d_anchor.get() + (size_t)p * 3 * PMAF_FTRACK_LANES, rad};
 }
 
-// the launch: set A against set B into the scratch, the step matrices where they are wanted
+// the launch: set A against set B into the scratch, the step matrices where they are wanted. Four kernels: step against
+// step or slacked, each with or without the attached terms
 static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *paths_a, const int32_t *len_a, int32_t n_a,
                           const double *paths_b, const int32_t *len_b, int32_t n_b, double separation,
                           const XAuditSlack *slack, bool want_a, bool want_b, const XAuditWindow *win = nullptr,
@@ -418,7 +424,22 @@ static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *pat
   A.separation = separation;
   A.clearance = B.clearance;
   A.step = want_a ? B.step : nullptr;
-  if (slack) {
+  if (slack && att) {   // the attached audit's terms over the slacked audit's band
+    CrossAuditAttachedSlackArgs U{};
+    CrossAuditAttachedArgs &T = U.T;
+    T.X = A;
+    T.a = attach_side(h, *att, att->pop_a);
+    T.b = attach_side(h, *att, att->pop_b);
+    T.pop_a = att->pop_a;
+    T.pop_b = att->pop_b;
+    T.M = h->D.n_obs - 1;
+    T.radius = h->D.C.rad;
+    T.sphere = att->want_sphere ? B.sphere : nullptr;
+    U.late_a = slack->late_a;
+    U.late_b = slack->late_b;
+    U.step_b = want_b ? B.step_b : nullptr;
+    pmaf_k_launch_cross_audit_attached_slack(U, h->stream);
+  } else if (slack) {
     S.late_a = slack->late_a;
     S.late_b = slack->late_b;
     S.step_b = want_b ? B.step_b : nullptr;
@@ -442,7 +463,8 @@ static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *pat
 
 // the matrix (and the step matrices the caller asked for) back to the host
 static void xaudit_download(pmaf_planner *h, const XAuditBuf &B, size_t pairs, double *clearance, int32_t *step_a,
-                            int32_t *step_b) {
+                            int32_t *step_b, int32_t *sphere = nullptr) {
+  if (sphere) HIP_CHECK(hipMemcpyAsync(sphere, B.sphere, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
   if (step_a) HIP_CHECK(hipMemcpyAsync(step_a, B.step, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
   if (step_b) HIP_CHECK(hipMemcpyAsync(step_b, B.step_b, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, h->stream));
   h->download(clearance, B.clearance, pairs);
@@ -459,7 +481,8 @@ static XAuditBuf cross_audit_populations(pmaf_planner *h, int32_t pop_a, int32_t
   clamp_slack(h, slack, who);
   h->use_device();
   if (!win) sync(h);   // behind the running rollout, like the getters of its results (the joint selection has waited)
-  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr || (att && att->want_sphere), win != nullptr);
+  const XAuditBuf B = xaudit_scratch(h, (size_t)D.N, (size_t)D.N, 0, slack != nullptr || (att && att->want_sphere), win != nullptr,
+                                     slack != nullptr && att && att->want_sphere);
   xaudit_launch(h, B, D.paths + (size_t)pop_a * D.N * D.cap * 3, D.n_points + (size_t)pop_a * D.N, D.N,
                 D.paths + (size_t)pop_b * D.N * D.cap * 3, D.n_points + (size_t)pop_b * D.N, D.N, separation, slack, want_a,
                 want_b, win, att);
@@ -547,6 +570,27 @@ int pmaf_cross_audit_attached(pmaf_planner *h, int32_t pop_a, int32_t pop_b, con
   });
 }
 
+int pmaf_cross_audit_attached_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
+                                    int32_t late_a, int32_t late_b, double *clearance, int32_t *step_a, int32_t *step_b,
+                                    int32_t *sphere) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_cross_audit_attached_slack: NULL argument");
+    const DevView &D = h->D;
+    if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
+      fail(PMAF_ERR_INVALID, "pmaf_cross_audit_attached_slack: need two different populations of the handle");
+    check_range(&separation, 1, "separation");
+    XAuditSlack slack{late_a, late_b};
+    clamp_slack(h, &slack, "pmaf_cross_audit_attached_slack");
+    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+    h->use_device();
+    sync(h);   // behind the running rollout; the list's upload below is in stream order behind it
+    const XAuditAttach T{pop_a, pop_b, upload_plan_obstacles(h, obstacles), sphere != nullptr};
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, &slack, step_a != nullptr, step_b != nullptr,
+                                                "pmaf_cross_audit_attached_slack", nullptr, &T);
+    xaudit_download(h, B, (size_t)D.N * D.N, clearance, step_a, step_b, sphere);
+  });
+}
+
 int pmaf_cross_audit_tracks(pmaf_planner *h, int32_t pop, int32_t n_tracks, const double *tracks,
                             const int32_t *n_track_points, double separation, double *clearance, int32_t *step) {
   return guarded([&] {
@@ -616,7 +660,9 @@ int pmaf_select_pair_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double
 // pmaf_select_pair_clear_tracked (include/pmaf.h, "joint selection on coupled handles") is the same path with a
 // TrackedCall: the obstacle side is then the tracked selection's audit (k_ft_select_audit, or k_ft_masked_audit where
 // columns of either list ride on the other member of the pair) and the pair side k_cross_audit_attached; a handle
-// without tracks and without such columns launches exactly what pmaf_select_pair_clear launches. ----
+// without tracks and without such columns launches exactly what pmaf_select_pair_clear launches.
+// pmaf_select_pair_clear_tracked_slack passes `late` as well: the pair side is then k_xaudit_attached_slack where columns
+// ride on the other member, and k_cross_audit_slack where none does. ----
 struct PairClearSideB {
   int32_t pop_b, n_tracks;
   const double *tracks;
@@ -748,6 +794,24 @@ int pmaf_select_pair_clear_tracked(pmaf_planner *h, int32_t pop_a, int32_t pop_b
     const TrackedCall T{first, "pmaf_select_pair_clear_tracked"};
     select_pair_clear(h, pop_a, PairClearSideB{pop_b, 0, nullptr, nullptr, nullptr}, obstacles, obstacle_margin, horizon,
                       skip_trailing, separation, pair_margin, nullptr, prev_pair, adopt,
+                      PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
+                                   first_violation, worst_excess, pair_steps},
+                      T.who, &T);
+  });
+}
+
+int pmaf_select_pair_clear_tracked_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles,
+                                         const int32_t *first, double obstacle_margin, int32_t horizon, int32_t skip_trailing,
+                                         double separation, double pair_margin, const int32_t *late, const int32_t *prev_pair,
+                                         int32_t adopt, int32_t *pair, int32_t *rule, int32_t *n_feasible, int32_t *n_clear,
+                                         double *pair_cost, double *pair_clearance, double *obstacle_clearance,
+                                         int32_t *first_violation, double *worst_excess, int32_t *pair_steps) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && pair, "pmaf_select_pair_clear_tracked_slack: NULL argument");
+    REQUIRE(pop_b >= 0, "pmaf_select_pair_clear_tracked_slack: need two different populations of the handle");
+    const TrackedCall T{first, "pmaf_select_pair_clear_tracked_slack"};
+    select_pair_clear(h, pop_a, PairClearSideB{pop_b, 0, nullptr, nullptr, nullptr}, obstacles, obstacle_margin, horizon,
+                      skip_trailing, separation, pair_margin, late, prev_pair, adopt,
                       PairClearOut{pair, rule, n_feasible, n_clear, pair_cost, pair_clearance, obstacle_clearance,
                                    first_violation, worst_excess, pair_steps},
                       T.who, &T);

@@ -1,7 +1,7 @@
 // pmaf_xattach.hpp -- the cross audit on coupled handles (include/pmaf.h "joint selection on coupled handles":
-// pmaf_cross_audit_attached, pmaf_select_pair_clear_tracked): the structs and the launch interface between
-// pmaf_host_audit.cpp and the two kernels the calls add -- k_cross_audit_attached (pmaf_k_xattach.hip) and
-// k_ft_masked_audit (pmaf_k_auditft.hip). A header of its own so that no other kernel unit's inputs change with it:
+// pmaf_cross_audit_attached, pmaf_select_pair_clear_tracked, and their slacked forms): the structs and the launch interface
+// between pmaf_host_audit.cpp and the kernels the calls add -- k_cross_audit_attached (pmaf_k_xattach.hip),
+// k_xaudit_attached_slack (pmaf_k_xattach_slack.hip) and k_ft_masked_audit (pmaf_k_auditft.hip). A header of its own so that no other kernel unit's inputs change with it:
 // CrossAuditArgs, SelectArgs and FTrackArgs stay what they are.
 #pragma once
 #include "pmaf_types.hpp"
@@ -29,6 +29,18 @@ struct CrossAuditAttachedArgs {
 
 // pmaf_k_xattach.hip: k_cross_audit_attached on the cross audit's grid
 void pmaf_k_launch_cross_audit_attached(const CrossAuditAttachedArgs &A, hipStream_t s);
+
+// the attached audit with timing slack (include/pmaf.h "joint selection on coupled handles with timing slack":
+// pmaf_cross_audit_attached_slack, pmaf_select_pair_clear_tracked_slack): the terms above, every term over the slacked
+// audit's band. k is A's step and l B's in every term: T.X.step = step_a.
+struct CrossAuditAttachedSlackArgs {
+  CrossAuditAttachedArgs T;
+  int32_t *step_b;          // [n_a][n_b] or NULL
+  int late_a, late_b;       // 0 .. cap each (clamped on the host): admitted (k, l) iff -late_b <= l - k <= late_a
+};
+
+// pmaf_k_xattach_slack.hip: k_xaudit_attached_slack on the cross audit's grid
+void pmaf_k_launch_cross_audit_attached_slack(const CrossAuditAttachedSlackArgs &A, hipStream_t s);
 
 // the obstacle side's audited columns of the joint selection's two populations: bit j set = obstacle j of the list is
 // audited. Every other population of the handle keeps columns 0 .. SelectArgs::n_audit - 1. Handed to the tracked audit's

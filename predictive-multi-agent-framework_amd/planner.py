@@ -91,6 +91,11 @@ SYMBOLS = {
     "pmaf_cross_audit_attached": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, C.c_double, _dp, _ip, _ip]),
     "pmaf_select_pair_clear_tracked": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32, C.c_double,
                                                  C.c_double, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _ip]),
+    "pmaf_cross_audit_attached_slack": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip,
+                                                  _ip]),
+    "pmaf_select_pair_clear_tracked_slack": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32,
+                                                       C.c_double, C.c_double, _ip, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp,
+                                                       _dp, _dp, _ip, _dp, _ip]),
     "pmaf_get_paths": (C.c_int, [_V, _dp, _ip]),
     "pmaf_view_paths": (C.c_int, [_V, C.POINTER(_dp), C.POINTER(_ip)]),
     "pmaf_get_costs": (C.c_int, [_V, _dp]),
@@ -906,13 +911,35 @@ class PmafPlanner:
         out = (clr,) + ((st,) if step else ()) + ((sp,) if sphere else ())
         return out if len(out) > 1 else clr
 
+    def cross_audit_attached_slack(self, pop_a, pop_b, obstacles, separation, late_a, late_b, steps=False, sphere=False):
+        """cross_audit_attached over the slacked audit's band: every term of a pair over the pairs of steps (k, l) with
+        -late_b <= l - k <= late_a (pmaf_cross_audit_attached_slack). clearance [N][N], followed by step_a, step_b
+        (steps=True) and / or sphere where asked for (int32 [N][N])"""
+        clr = np.zeros((self.N, self.N))
+        sa = np.zeros((self.N, self.N), dtype=np.int32) if steps else None
+        sb = np.zeros((self.N, self.N), dtype=np.int32) if steps else None
+        sp = np.zeros((self.N, self.N), dtype=np.int32) if sphere else None
+        self._chk(self.L.pmaf_cross_audit_attached_slack(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)),
+                                                         float(separation), int(late_a), int(late_b), _p(clr), _pi(sa),
+                                                         _pi(sb), _pi(sp)))
+        out = (clr,) + ((sa, sb) if steps else ()) + ((sp,) if sphere else ())
+        return out if len(out) > 1 else clr
+
     def select_pair_clear_tracked(self, pop_a, pop_b, obstacles, obstacle_margin, horizon, separation, pair_margin,
-                                  skip_trailing=False, prev_pair=None, adopt=False, first=None):
+                                  skip_trailing=False, prev_pair=None, adopt=False, first=None, late=None):
         """select_pair_clear on a coupled / tracked handle (pmaf_select_pair_clear_tracked): the obstacle side is
         select_clear_tracked's (tracks read from `first`) without the columns that ride on the other member of the pair,
-        the pair side is cross_audit_attached's on the windows; the same dict"""
+        the pair side is cross_audit_attached's on the windows; the same dict. late = (late_a, late_b): the pair side
+        is cross_audit_attached_slack's (pmaf_select_pair_clear_tracked_slack); None calls the un-slacked export"""
         o, args = self._joint_outputs()
         pv = self._pair_arg(prev_pair)
+        if late is not None:
+            self._chk(self.L.pmaf_select_pair_clear_tracked_slack(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)),
+                                                                  _pi(self._first(first)), float(obstacle_margin), int(horizon),
+                                                                  1 if skip_trailing else 0, float(separation),
+                                                                  float(pair_margin), _pi(self._pair_arg(late)), _pi(pv),
+                                                                  1 if adopt else 0, *args))
+            return self._joint_dict(o)
         self._chk(self.L.pmaf_select_pair_clear_tracked(self._h, int(pop_a), int(pop_b), _p(self._obs(obstacles)),
                                                         _pi(self._first(first)), float(obstacle_margin), int(horizon),
                                                         1 if skip_trailing else 0, float(separation), float(pair_margin),

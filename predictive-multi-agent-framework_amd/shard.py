@@ -154,10 +154,12 @@ class DualArmCoupling:
         `horizon` points of both paths (pmaf_select_pair_clear, include/pmaf.h "joint selection"): each arm's trailing
         sphere at the other arm's last set-point is left to the cross audit (skip_trailing), the previous tick's pair is
         the hysteresis reference, and adopt is carried out by the same call. The dict is select_pair_clear's plus
-        feasible (rule 0 or 1) and positions. None: as before. With tracked=True in the dict (and late=None) the pair is
+        feasible (rule 0 or 1) and positions. None: as before. With tracked=True in the dict the pair is
         picked by pmaf_select_pair_clear_tracked (include/pmaf.h "joint selection on coupled handles"): both arms are
         audited against the obstacle tracks the rollouts followed (first=... in the dict: the offsets, default the
-        handle's), and the pair against the spheres that `field` attaches, riding on the candidate that is being picked.
+        handle's), and the pair against the spheres that `field` attaches, riding on the candidate that is being picked;
+        with `late` given too, every sphere is held over the slack band (pmaf_select_pair_clear_tracked_slack: a sphere
+        that rides on arm 1 is on arm 1's clock).
         tracks = shift: the rollouts this tick starts follow the other arm's selected path from point `shift` on instead of
         the sphere at rest (pmaf_couple_tracks, include/pmaf.h "repulsive track"; with adopt=True the pair's paths, else
         evaluate's own selections). coupled_obstacles is left as it is: the sphere at the last set-point stays in the
@@ -190,10 +192,9 @@ class DualArmCoupling:
         if clear is not None:
             obs = self.coupled_obstacles(planner.real_state()[0], advance)
             if clear.get("tracked"):
-                assert late is None, "the tracked joint selection has no timing slack"
                 out = planner.select_pair_clear_tracked(0, 1, obs, clear["margin"], clear["horizon"], agent_radius + self.radius,
                                                         margin, skip_trailing=True, prev_pair=self.prev_pair, adopt=adopt,
-                                                        first=clear.get("first"))
+                                                        first=clear.get("first"), late=late)
             else:
                 out = planner.select_pair_clear(0, 1, obs, clear["margin"], clear["horizon"], agent_radius + self.radius, margin,
                                                 skip_trailing=True, late=late, prev_pair=self.prev_pair, adopt=adopt)

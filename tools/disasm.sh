@@ -1,6 +1,6 @@
 #!/bin/bash
 # disassembles the gfx950 code object of a kernel object file: tools/disasm.sh <lib/obj/k_*.o> <out.s>
-# (any kernel object: the twelve k_*.o and slack.o, dbgmath.o, select.o, pairclear.o, track.o, ftrack.o, auditft.o, fcouple.o, xattach.o;
+# (any kernel object: the twelve k_*.o and slack.o, dbgmath.o, select.o, pairclear.o, track.o, ftrack.o, auditft.o, fcouple.o, xattach.o, xattach_slack.o;
 # tools/disasm_diff.sh compares two builds' objects through this script)
 set -e
 LLVM=/opt/rocm/lib/llvm/bin
