@@ -60,6 +60,7 @@ struct PathAudit {
   std::vector<int> step;             // path point at which it is reached (-1: no comparable pair)
   std::vector<int> obstacle;         // ... and the obstacle it is reached against
   std::vector<int> first_violation;  // first path point with a clearance below the margin; the path's size if none
+  std::vector<int> obstacle_step;    // evaluatePathsSlack only: the OBSTACLES' time index of the closest approach (step = the arm's)
 };
 
 // result of CfManager::crossAudit: this manager's predicted paths against another arm's (pmaf.h, "cross audit")
@@ -497,6 +498,29 @@ class CfManager {
     const int32_t f = trackedFirst(first, "evaluatePathsTracked");
     return evaluatePathsImpl(obstacles, margin, true, first.empty() ? nullptr : &f, "evaluatePathsTracked");
   }
+  // ... with timing slack: the arm may run up to `late` steps behind the obstacles' clock, the obstacles up to `early`
+  // behind the arm's (pmaf_evaluate_paths_slack, include/pmaf.h "clear selection with timing slack"). step and
+  // first_violation are the ARM'S steps, obstacle_step the obstacles' index of the closest admitted pair. Tracks, offset,
+  // trailing obstacle and radii as evaluatePathsTracked. std::out_of_range for a negative slack.
+  PathAudit evaluatePathsSlack(const std::vector<Obstacle> &obstacles, const double margin, const int late, const int early,
+                               const std::vector<int> &first = {}) {
+    if (late < 0 || early < 0) throw std::out_of_range("evaluatePathsSlack: a slack must be >= 0");
+    const int32_t f = trackedFirst(first, "evaluatePathsSlack");
+    require();
+    if ((int)obstacles.size() != n_obs_) throw std::out_of_range("evaluatePathsSlack: obstacle count changed");
+    const std::vector<double> obs = flat(obstacles);
+    PathAudit r;
+    r.clearance.resize(n_agents_);
+    std::vector<int32_t> st(n_agents_), os(n_agents_), ob(n_agents_), fv(n_agents_);
+    check(pmaf_evaluate_paths_slack(h_, obs.data(), first.empty() ? nullptr : &f, margin, late, early, r.clearance.data(),
+                                    st.data(), os.data(), ob.data(), fv.data()),
+          "evaluatePathsSlack");
+    r.step.assign(st.begin(), st.end());
+    r.obstacle_step.assign(os.begin(), os.end());
+    r.obstacle.assign(ob.begin(), ob.end());
+    r.first_violation.assign(fv.begin(), fv.end());
+    return r;
+  }
   // The other arm of a bimanual node is a second CfManager: every predicted path of THIS manager against every path of
   // `other_paths` (the other manager's getPredictedPaths(), or its selected path alone), both on the same step grid, an
   // ended path held at its last point (pmaf_cross_audit_tracks; no reference equivalent). separation = the sum of the
@@ -626,19 +650,34 @@ class CfManager {
     return selectClearImpl(obstacles, margin, horizon, adopt, true, first.empty() ? nullptr : &f, skip_trailing,
                            "selectClearTracked");
   }
+  // ... with timing slack: the arm may run up to `late` steps behind the obstacles' clock, the obstacles up to `early`
+  // behind the arm's (pmaf_select_clear_slack, include/pmaf.h "clear selection with timing slack"); everything else as
+  // selectClearTracked. std::out_of_range for a negative slack.
+  ClearSelection selectClearSlack(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
+                                  const int late, const int early, const bool adopt = true,
+                                  const std::vector<int> &first = {}, const bool skip_trailing = false) {
+    if (late < 0 || early < 0) throw std::out_of_range("selectClearSlack: a slack must be >= 0");
+    const int32_t f = trackedFirst(first, "selectClearSlack");
+    const int32_t slack[2] = {late, early};
+    return selectClearImpl(obstacles, margin, horizon, adopt, true, first.empty() ? nullptr : &f, skip_trailing,
+                           "selectClearSlack", slack);
+  }
 
  private:
-  // one body behind selectClear and selectClearTracked (first: the offset or NULL)
+  // one body behind selectClear, selectClearTracked and selectClearSlack (first: the offset or NULL; slack: (late,
+  // early) or NULL)
   ClearSelection selectClearImpl(const std::vector<Obstacle> &obstacles, const double margin, const int horizon,
                                  const bool adopt, const bool tracked, const int32_t *first, const bool skip_trailing,
-                                 const char *who) {
+                                 const char *who, const int32_t *slack = nullptr) {
     require();
     if ((int)obstacles.size() != n_obs_) throw std::out_of_range(std::string(who) + ": obstacle count changed");
     const std::vector<double> obs = flat(obstacles);
     const int32_t prev = prev_pick_;
     int32_t pick = -1, rule = -1, n_clear = 0, fv = 0;
     ClearSelection r;
-    check(tracked ? pmaf_select_clear_tracked(h_, obs.data(), first, margin, horizon, skip_trailing ? 1 : 0, &prev,
+    check(slack ? pmaf_select_clear_slack(h_, obs.data(), first, margin, horizon, skip_trailing ? 1 : 0, slack[0], slack[1],
+                                          &prev, adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost, &r.clearance, &fv)
+          : tracked ? pmaf_select_clear_tracked(h_, obs.data(), first, margin, horizon, skip_trailing ? 1 : 0, &prev,
                                               adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost, &r.clearance, &fv)
                   : pmaf_select_clear(h_, obs.data(), margin, horizon, &prev, adopt ? 1 : 0, &pick, &rule, &n_clear, &r.cost,
                                       &r.clearance, &fv),
@@ -708,15 +747,20 @@ class CfManager {
   // planCallback's sequence with the selection held against the live list: stopPrediction, evaluateAgents,
   // selectClear(adopt), moveRealEEAgent(agent_id = pick), resetEEAgents to the new set-point, startPrediction. Returns
   // the pick. tracked: the selection is selectClearTracked -- against the obstacle tracks the rollouts followed, at the
-  // offset they are at (advanceObstacleTracks between two ticks moves both on).
+  // offset they are at (advanceObstacleTracks between two ticks moves both on). late / early: with either non-zero the
+  // selection is selectClearSlack -- the arm up to `late` steps behind the obstacles' clock, the obstacles up to `early`
+  // behind the arm's; it reads the attached tracks whatever `tracked` says. With both zero the calls are exactly what
+  // they are without the two parameters.
   int planTickAudited(const std::vector<Obstacle> &obstacles, const double delta_t, const double k_goal_dist,
                       const double k_path_len, const double k_safe_dist, const double k_workspace,
                       const Vector6d des_ws_limits, const double margin, const int horizon,
-                      Vector3d *next_position = nullptr, ClearSelection *sel = nullptr, const bool tracked = false) {
+                      Vector3d *next_position = nullptr, ClearSelection *sel = nullptr, const bool tracked = false,
+                      const int late = 0, const int early = 0) {
     stopPrediction();
     evaluateAgents(obstacles, k_goal_dist, k_path_len, k_safe_dist, k_workspace, des_ws_limits);
-    const ClearSelection s = tracked ? selectClearTracked(obstacles, margin, horizon, true)
-                                     : selectClear(obstacles, margin, horizon, true);
+    const ClearSelection s = (late != 0 || early != 0) ? selectClearSlack(obstacles, margin, horizon, late, early, true)
+                             : tracked                 ? selectClearTracked(obstacles, margin, horizon, true)
+                                                       : selectClear(obstacles, margin, horizon, true);
     moveRealEEAgent(obstacles, delta_t, 1, s.pick);
     double p[3], v[3];
     check(pmaf_get_real_state(h_, p, v, nullptr), "planTickAudited");

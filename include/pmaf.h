@@ -696,6 +696,70 @@ int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const in
                               int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
                               int32_t *first_violation);
 
+/* ---- clear selection with timing slack: an arm that runs late stays clear (exports added under ABI 7) ----
+ * Every audit above holds step k of a predicted path against step k of the obstacles, as if both were one instant. On a
+ * robot they are not: the real end effector trails its set-points (the closed-loop scenarios run with a 30 % tracking
+ * lag), and a motion predictor's clock is not the controller's. The cross audit with timing slack answers that for arm
+ * against arm; these two calls answer it for arm against obstacles, which is where the obstacle tracks put a
+ * time-indexed prediction into the planner: a path that passes behind a moving obstacle is clear step against step and
+ * is hit when the arm is three steps late. No reference equivalent.
+ * Carried over unchanged from pmaf_evaluate_paths_tracked and pmaf_select_clear_tracked: the window w (n for the
+ * evaluate call, min(n, horizon) for the selection); first ([P] or NULL, clamped to L-1 before anything is added, may be
+ * INT32_MAX, an entry below 0 PMAF_ERR_INVALID, first != NULL on a handle without tracks PMAF_ERR_STATE); a population
+ * with L == 0, and a handle without tracks, are on the list's iterated line; the trailing obstacle stays on the list's
+ * line and is left out with skip_trailing != 0 (the selection only); radius + r_j with r_j from the CALLER'S list; the
+ * build's dot association; rules 0 / 1 / 2 with the 0.9 hysteresis; adopt, the wait for a running rollout, the refusal of
+ * a handle whose tick was abandoned (the selection; PMAF_ERR_STATE until pmaf_stop), no state change with adopt == 0 (a
+ * tick sequence with such calls in between is bit-identical to one without); which outputs may be NULL.
+ * The one change: the obstacles have a time index l of their own.
+ *   late >= 0:   the arm may be up to `late` steps BEHIND the obstacles' clock: it stands at x_k while they are at index
+ *                k + s, 0 <= s <= late.
+ *   early >= 0:  the obstacles may be up to `early` steps behind the arm's clock (a predictor that leads, an arm ahead of
+ *                schedule): the arm at x_k, they at index k - s, 0 <= s <= early.
+ *   admitted:    the pairs (k, l) with 0 <= k < w, l >= 0 and -early <= l - k <= late. l has no upper bound of its own:
+ *                obstacles do not end where the path does.
+ *   tracked field obstacle (L > 0, j < M) at index l: the POSITION of track point min(min(f, L-1) + l, L-1), taken
+ *                verbatim and held at the end (the hold applies to the slacked index, not before the slack is added).
+ *   every other obstacle at index l: on the list's chain o^0 = the caller's position, o^{l+1} = o^l + RN(v dt) per
+ *                component. The chain is walked from o^0 and never multiplied out: o^l has the bits of
+ *                pmaf_evaluate_paths' track for every l, also for l >= w.
+ *   c(k,l,j)   = norm(x_k - o_j^l) - (radius + r_j)
+ *   clearance_a = the minimum of c over the admitted (k, l) and the audited j under the total order (c, k, l, j): ties go
+ *                to the smallest k, then the smallest l, then the smallest j. A NaN never wins and never violates. When
+ *                nothing won (an empty window, nothing audited, NaN or +infinity everywhere): +infinity with
+ *                (step, obstacle_step, obstacle) = (-1, -1, -1). step = k, obstacle_step = l, obstacle = j.
+ *   first_violation_a = the smallest k < w for which some admitted l and audited j have c(k,l,j) < margin, else w. It
+ *                reports the ARM'S step, not the obstacles' index.
+ * late < 0 or early < 0: PMAF_ERR_INVALID. Values of max_prediction_steps or more are clamped to it on the host, before
+ * any device arithmetic: the clamped value is the slack of the call (an `early` of that size already reaches index 0
+ * from every point of the window; a `late` of that size is a whole rollout behind). Then l < 2 * max_prediction_steps
+ * and no index can overflow.
+ * Consequences:
+ *   - (late, early) = (0, 0) gives pmaf_evaluate_paths_tracked's and pmaf_select_clear_tracked's outputs bit for bit, with
+ *     obstacle_step == step (through this block's own kernel all the same);
+ *   - clearance, first_violation and n_clear never grow when either slack grows;
+ *   - a list at rest on a handle without tracks gives the unslacked bits for every slack (every index is one place);
+ *     obstacle_step is then the band's first index, max(step - early, 0).
+ * pmaf_evaluate_paths_slack: clearance [P][N] is required; step, obstacle_step, obstacle, first_violation [P][N] may each
+ * be NULL. Every obstacle of the list is audited, the trailing one included. There is no per_obstacle output.
+ * pmaf_select_clear_slack: pick [P] is required; rule, n_clear, cost, clearance, first_violation [P] may each be NULL;
+ * horizon and prev_idx are validated as in pmaf_select_clear.
+ * Cost: every obstacle position is held against late + early + 1 path points instead of one; horizon is the caller's
+ * lever at tick rate (profiles/obstacle_slack_audit.md).
+ * Out of scope, and so still step against step: per_obstacle, and the obstacle side of the pair selections
+ * (pmaf_select_pair_clear and its tracked and slacked forms, pmaf_select_clear_tracks) -- their `late` is the arms' slack
+ * against each other only.
+ * Intended six-call tick (CfManager::planTickAudited(..., tracked = true, late, early)):
+ *   pmaf_stop -> pmaf_evaluate -> pmaf_select_clear_slack(adopt = 1) -> pmaf_move_real(agent_id = pick)
+ *   -> pmaf_reset_agents -> [pmaf_set_obstacle_track_offset] -> pmaf_start */
+int pmaf_evaluate_paths_slack(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin,
+                              int32_t late, int32_t early, double *clearance, int32_t *step, int32_t *obstacle_step,
+                              int32_t *obstacle, int32_t *first_violation);
+int pmaf_select_clear_slack(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin,
+                            int32_t horizon, int32_t skip_trailing, int32_t late, int32_t early,
+                            const int32_t *prev_idx, int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear,
+                            double *cost, double *clearance, int32_t *first_violation);
+
 /* ---- joint selection on coupled handles: pairs held to the riding spheres (exports added under ABI 7) ----
  * pmaf_couple_obstacle_tracks puts spheres of one arm's list on the OTHER arm's selected path (gripper, load, forearm
  * spheres at anchor + scale * point) and the rollouts bend round them. pmaf_select_pair_clear then picks the pair

@@ -48,6 +48,12 @@
 #                        the attached audit's terms over the slacked audit's band, compiled with the plain kernel flags
 #                        (-ffp-contract=off, as xattach.o); a unit of its own for the same reason, object xattach_slack.o
 #                        (tests/test_attached_slack_audit.py holds its kernel to no scratch through the resource record)
+#   pmaf_k_obslack.hip   the audits against the live list with timing slack (pmaf_evaluate_paths_slack /
+#                        pmaf_select_clear_slack): k_obs_slack_audit<false|true>, the body of pmaf_obstacle_slack.hpp (which
+#                        takes ft_window from pmaf_select_audit.hpp), compiled with the plain kernel flags
+#                        (-ffp-contract=off, as auditft.o); a unit of its own for the same reason, object obslack.o,
+#                        outside the k_*.o set like slack.o
+#                        (tests/test_obstacle_slack_audit.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_dbgmath.hip   ops 13..20 of pmaf_debug_math (test support: the policies' elementary operations that ops 0..12 in
 #                        pmaf_k_misc.hip do not reach), a unit of its own for the same reason; its object is dbgmath.o
 #   pmaf_host.cpp        the C-ABI (g++, plain C++ against the HIP runtime API): handle, tick protocol, repulsive track,
@@ -102,6 +108,7 @@ DEPS_SELECT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_select_audit.hpp"   # ... and p
 DEPS_AUDITFT="$DEPS_SELECT pmaf_audit_chain.hpp pmaf_auditft.hpp pmaf_xattach.hpp"   # ... and pmaf_k_auditft.hip
 DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach.hip
 DEPS_XATTACH_SLACK="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach_slack.hip
+DEPS_OBSLACK="$DEPS_SELECT pmaf_obstacle_slack.hpp"   # ... and pmaf_k_obslack.hip
 DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
@@ -120,6 +127,7 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   [ "$src" = pmaf_k_select.hip ] && extra=$DEPS_SELECT
   [ "$src" = pmaf_k_auditft.hip ] && extra=$DEPS_AUDITFT
   [ "$src" = pmaf_k_fcouple.hip ] && extra=$DEPS_FCOUPLE
+  [ "$src" = pmaf_k_obslack.hip ] && extra=$DEPS_OBSLACK
   [ "$src" = pmaf_k_xattach.hip ] && extra=$DEPS_XATTACH
   [ "$src" = pmaf_k_xattach_slack.hip ] && extra=$DEPS_XATTACH_SLACK
   for d in $src $DEPS_K $extra build.sh; do [ "$d" -nt "$o" ] && stale=1; done
@@ -159,6 +167,7 @@ kcompile dbgmath pmaf_k_dbgmath.hip
 kcompile fcouple pmaf_k_fcouple.hip
 kcompile xattach pmaf_k_xattach.hip
 kcompile xattach_slack pmaf_k_xattach_slack.hip
+kcompile obslack pmaf_k_obslack.hip
 # (the flags of k_w64_m2_t1: the same body)
 kcompile track pmaf_k_track.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
 kcompile ftrack pmaf_k_ftrack.hip -DPMAF_W64_MATH=2 -falign-loops=32 -DPMAF_SUM_TAIL_PIN=1
@@ -175,8 +184,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o "$OBJ"/xattach.o "$OBJ"/xattach_slack.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o "$OBJ"/xattach.o "$OBJ"/xattach_slack.o "$OBJ"/obslack.o \
   $(for u in $HOST_UNITS; do echo "$OBJ/$u.o"; done) -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log "$OBJ"/xattach.log "$OBJ"/xattach_slack.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log "$OBJ"/xattach.log "$OBJ"/xattach_slack.log "$OBJ"/obslack.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

@@ -4,6 +4,7 @@
 #include "pmaf_host_impl.hpp"
 #include "pmaf_auditft.hpp"
 #include "pmaf_xattach.hpp"
+#include "pmaf_obstacle_slack.hpp"
 
 extern "C" {
 
@@ -31,6 +32,19 @@ struct TrackedCall {
 };
 static void check_tracked_first(const pmaf_planner *h, const TrackedCall &T);
 static FTrackArgs tracked_args(pmaf_planner *h, const TrackedCall &T);
+// the slacked calls against the live list (include/pmaf.h "clear selection with timing slack"): the arm up to `late`
+// steps behind the obstacles' clock, the obstacles up to `early` behind the arm's. A null pointer is the call without
+// slack; (0, 0) is a slacked call like any other and runs k_obs_slack_audit.
+struct ObstacleSlack {
+  int32_t late, early;
+};
+// host-side validation, before any wait. A slack of cap or more is clamped to cap here, before any device arithmetic
+// (the contract's rule: then l < 2 cap on the device).
+static ObstacleSlack clamp_obstacle_slack(const pmaf_planner *h, int32_t late, int32_t early, const std::string &who) {
+  if (late < 0 || early < 0) fail(PMAF_ERR_INVALID, who + ": late and early must be >= 0");
+  const int32_t cap = h->D.cap;
+  return ObstacleSlack{late < cap ? late : cap, early < cap ? early : cap};
+}
 
 static void evaluate_paths(pmaf_planner *h, const double *obstacles, double margin, bool only_best, double *clearance,
                            int32_t *step, int32_t *obstacle, int32_t *first_violation, double *per_obstacle,
@@ -96,6 +110,59 @@ int pmaf_evaluate_paths_tracked(pmaf_planner *h, const double *obstacles, const 
     REQUIRE(h && obstacles && clearance, "pmaf_evaluate_paths_tracked: NULL argument");
     const TrackedCall T{first, "pmaf_evaluate_paths_tracked"};
     evaluate_paths(h, obstacles, margin, false, clearance, step, obstacle, first_violation, per_obstacle, &T);
+  });
+}
+
+// the path audit with timing slack: the tracked audit's validation and staging (the list through
+// upload_plan_obstacles, the call's offsets through tracked_args), then ONE kernel, k_obs_slack_audit, on the whole
+// paths (horizon = cap) and every obstacle; its five outputs come back in one copy
+int pmaf_evaluate_paths_slack(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin, int32_t late,
+                              int32_t early, double *clearance, int32_t *step, int32_t *obstacle_step, int32_t *obstacle,
+                              int32_t *first_violation) {
+  return guarded([&] {
+    REQUIRE(h && obstacles && clearance, "pmaf_evaluate_paths_slack: NULL argument");
+    const TrackedCall T{first, "pmaf_evaluate_paths_slack"};
+    const DevView &D = h->D;
+    const ObstacleSlack slack = clamp_obstacle_slack(h, late, early, T.who);
+    check_tracked_first(h, T);
+    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+    check_range(&margin, 1, "margin");
+    h->use_device();
+    sync(h);   // behind the running rollout, like the getters of its results
+    const size_t rows = (size_t)D.P * D.N;
+    const size_t bytes = sizeof(double) * rows + 4 * sizeof(int32_t) * rows;
+    h->d_oslack.reserve(bytes);
+    h->h_oslack.reserve(bytes);
+    ObsSlackArgs A{};
+    A.obs = upload_plan_obstacles(h, obstacles);
+    A.margin = margin;
+    A.horizon = D.cap;
+    A.n_audit = D.n_obs;
+    A.late = slack.late;
+    A.early = slack.early;
+    char *d_out = h->d_oslack.get();
+    A.clr = reinterpret_cast<double *>(d_out);
+    int32_t *ints = reinterpret_cast<int32_t *>(d_out + sizeof(double) * rows);
+    A.step = ints;
+    A.obstacle_step = ints + rows;
+    A.obstacle = ints + 2 * rows;
+    A.fv = ints + 3 * rows;
+    if (h->ftrk.on()) {   // (no tracks attached: every obstacle on the list's line)
+      const FTrackArgs F = tracked_args(h, T);
+      pmaf_k_launch_obs_slack_audit(D, A, &F, h->stream);
+    } else {
+      pmaf_k_launch_obs_slack_audit(D, A, nullptr, h->stream);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h->h_oslack.get(), d_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const char *src = h->h_oslack.get();
+    std::memcpy(clearance, src, sizeof(double) * rows); src += sizeof(double) * rows;
+    int32_t *const outs[4] = {step, obstacle_step, obstacle, first_violation};
+    for (int32_t *o : outs) {
+      if (o) std::memcpy(o, src, sizeof(int32_t) * rows);
+      src += sizeof(int32_t) * rows;
+    }
   });
 }
 
@@ -181,9 +248,11 @@ static void wait_select(pmaf_planner *h, const double *rec, int count, size_t re
 // the audit reads, then k_select_stage and ONE audit in stream order -- k_select_audit; in a tracked call on a handle with
 // tracks k_ft_select_audit (no tracks attached: the untracked audit, whose result it is); and k_ft_masked_audit where
 // `ride` names columns of two populations' lists that the caller leaves to its pair side (bit j set = column j is NOT
-// audited here). Returns the arguments, which a caller with a pick completes. Behind select_scratch().
+// audited here). With `oslack` (pmaf_select_clear_slack) the one audit is k_obs_slack_audit, with or without tracks, into
+// the same clr / fv. Returns the arguments, which a caller with a pick completes. Behind select_scratch().
 static SelectArgs select_obstacle_side(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon,
-                                       bool skip_trailing, const TrackedCall *tracked, const AuditColumns *ride = nullptr) {
+                                       bool skip_trailing, const TrackedCall *tracked, const AuditColumns *ride = nullptr,
+                                       const ObstacleSlack *oslack = nullptr) {
   const DevView &D = h->D;
   aos_to_soa(obstacles, h->sel.host(), D.P, D.n_obs);
   SelectArgs A{};
@@ -198,7 +267,18 @@ static SelectArgs select_obstacle_side(pmaf_planner *h, const double *obstacles,
   FTrackArgs F{};
   if (ft) F = tracked_args(h, *tracked);
   pmaf_k_launch_select_stage(D, A, h->stream);
-  if (!ft) {
+  if (oslack) {
+    ObsSlackArgs O{};
+    O.obs = A.obs;
+    O.margin = A.margin;
+    O.horizon = A.horizon;
+    O.n_audit = A.n_audit;
+    O.late = oslack->late;
+    O.early = oslack->early;
+    O.clr = A.clr;
+    O.fv = A.fv;
+    pmaf_k_launch_obs_slack_audit(D, O, ft ? &F : nullptr, h->stream);
+  } else if (!ft) {
     pmaf_k_launch_select_audit(D, A, h->stream);
   } else if (ride && (ride->cols_a | ride->cols_b) != 0) {
     const uint64_t all = A.n_audit >= 64 ? ~(uint64_t)0 : ((uint64_t)1 << A.n_audit) - 1;
@@ -211,11 +291,13 @@ static SelectArgs select_obstacle_side(pmaf_planner *h, const double *obstacles,
   return A;
 }
 
-// One body behind pmaf_select_clear and pmaf_select_clear_tracked (tracked != NULL; n_audit = n_obs, or n_obs - 1 when
-// the tracked call skips the trailing obstacle). Called inside guarded().
+// One body behind pmaf_select_clear, pmaf_select_clear_tracked (tracked != NULL; n_audit = n_obs, or n_obs - 1 when
+// the tracked call skips the trailing obstacle) and pmaf_select_clear_slack (tracked and oslack != NULL). Called inside
+// guarded().
 static void select_clear(pmaf_planner *h, const double *obstacles, double margin, int32_t horizon, const int32_t *prev_idx,
                          int32_t adopt, int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
-                         int32_t *first_violation, const std::string &who, const TrackedCall *tracked, bool skip_trailing) {
+                         int32_t *first_violation, const std::string &who, const TrackedCall *tracked, bool skip_trailing,
+                         const ObstacleSlack *oslack = nullptr) {
   REQUIRE(h && obstacles && pick, who + ": NULL argument");
   const DevView &D = h->D;
   REQUIRE(horizon >= 1, who + ": horizon must be >= 1");
@@ -232,7 +314,7 @@ static void select_clear(pmaf_planner *h, const double *obstacles, double margin
   double *rec = h->sel.host() + list;
   int32_t *prev_h = reinterpret_cast<int32_t *>(rec + (size_t)D.P * PMAF_SELECT_REC);
   if (prev_idx) std::memcpy(prev_h, prev_idx, sizeof(int32_t) * (size_t)D.P);
-  SelectArgs A = select_obstacle_side(h, obstacles, margin, horizon, skip_trailing, tracked);
+  SelectArgs A = select_obstacle_side(h, obstacles, margin, horizon, skip_trailing, tracked, nullptr, oslack);
   A.adopt = adopt ? 1 : 0;
   A.prev = prev_idx ? reinterpret_cast<const int32_t *>(h->sel.dev() + list + (size_t)D.P * PMAF_SELECT_REC) : nullptr;
   A.result = h->sel.dev() + list;
@@ -268,6 +350,19 @@ int pmaf_select_clear_tracked(pmaf_planner *h, const double *obstacles, const in
     const TrackedCall T{first, "pmaf_select_clear_tracked"};
     select_clear(h, obstacles, margin, horizon, prev_idx, adopt, pick, rule, n_clear, cost, clearance, first_violation,
                  T.who, &T, skip_trailing != 0);
+  });
+}
+
+int pmaf_select_clear_slack(pmaf_planner *h, const double *obstacles, const int32_t *first, double margin, int32_t horizon,
+                            int32_t skip_trailing, int32_t late, int32_t early, const int32_t *prev_idx, int32_t adopt,
+                            int32_t *pick, int32_t *rule, int32_t *n_clear, double *cost, double *clearance,
+                            int32_t *first_violation) {
+  return guarded([&] {
+    const TrackedCall T{first, "pmaf_select_clear_slack"};
+    REQUIRE(h && obstacles && pick, std::string(T.who) + ": NULL argument");
+    const ObstacleSlack slack = clamp_obstacle_slack(h, late, early, T.who);
+    select_clear(h, obstacles, margin, horizon, prev_idx, adopt, pick, rule, n_clear, cost, clearance, first_violation,
+                 T.who, &T, skip_trailing != 0, &slack);
   });
 }
 

@@ -245,6 +245,10 @@ struct pmaf_planner {
   // pmaf_cross_audit / pmaf_cross_audit_tracks / pmaf_select_pair scratch, grown on demand: the clearance matrix and the
   // step matrix, the pair reduction's partials and result, the caller's tracks and their lengths
   DeviceBuf<char> d_xaudit;
+  // pmaf_evaluate_paths_slack scratch, grown on demand: the five per-agent outputs on the device and their pinned host
+  // mirror (pmaf_select_clear_slack needs neither: its audit writes the selection's d_sel_clr / d_sel_fv)
+  DeviceBuf<char> d_oslack;
+  PinnedBuf<char> h_oslack;
   // pmaf_select_clear / pmaf_adopt_best scratch, allocated by the first call; none of it is planner state. Mapped pinned
   // host memory of the call's own (`sel`, NOT `zc`: the list must not become the resident live list): the list [P][7][n_obs] |
   // the result records [P][PMAF_SELECT_REC] | the previous picks [P] int32. On the device: the staged list, the audit's

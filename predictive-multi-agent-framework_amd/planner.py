@@ -88,6 +88,9 @@ SYMBOLS = {
     "pmaf_evaluate_paths_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, _dp, _ip, _ip, _ip, _dp]),
     "pmaf_select_clear_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp,
                                             _dp, _ip]),
+    "pmaf_evaluate_paths_slack": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _dp, _ip, _ip, _ip, _ip]),
+    "pmaf_select_clear_slack": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip, C.c_int32,
+                                          _ip, _ip, _ip, _dp, _dp, _ip]),
     "pmaf_cross_audit_attached": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, C.c_double, _dp, _ip, _ip]),
     "pmaf_select_pair_clear_tracked": (C.c_int, [_V, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.c_int32, C.c_double,
                                                  C.c_double, _ip, C.c_int32, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _ip]),
@@ -511,13 +514,17 @@ class PmafPlanner:
                                                   float(pair_margin), _pi(lt), _pi(pv), 1 if adopt else 0, *args))
         return self._joint_dict(o)
 
-    def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None, tracked=False):
+    def audited_tick(self, obstacles, dt, cost_gains, ws, margin, horizon, prev=None, tracked=False, late=0, early=0):
         """the six-call tick: stop, evaluate, select_clear(adopt), move_real(agent_id = pick), reset_agents to the new
         set-point, start. Returns select_clear's dict, with `best` = evaluate's own selection. tracked=True selects with
-        select_clear_tracked: against the attached obstacle tracks at the handle's offsets"""
+        select_clear_tracked: against the attached obstacle tracks at the handle's offsets. A non-zero late or early
+        selects with select_clear_slack (which reads the attached tracks whatever `tracked` says); with both zero the
+        calls are today's"""
         self.stop()
         best = self.evaluate(cost_gains, ws)
-        if tracked:
+        if late != 0 or early != 0:
+            sel = self.select_clear_slack(obstacles, margin, horizon, late, early, prev=prev, adopt=True)
+        elif tracked:
             sel = self.select_clear_tracked(obstacles, margin, horizon, prev=prev, adopt=True)
         else:
             sel = self.select_clear(obstacles, margin, horizon, prev=prev, adopt=True)
@@ -895,6 +902,33 @@ class PmafPlanner:
                                                    1 if skip_trailing else 0, _pi(pv), 1 if adopt else 0, _pi(out["pick"]),
                                                    _pi(out["rule"]), _pi(out["n_clear"]), _p(out["cost"]),
                                                    _p(out["clearance"]), _pi(out["first_violation"])))
+        return {k: (v[0].item() if self.P == 1 else v) for k, v in out.items()}
+
+    # -- clear selection with timing slack (include/pmaf.h "clear selection with timing slack") --
+    def evaluate_paths_slack(self, obstacles, margin=0.0, late=0, early=0, first=None):
+        """evaluate_paths_tracked with the arm up to `late` steps behind the obstacles' clock and the obstacles up to `early`
+        behind the arm's (pmaf_evaluate_paths_slack): clearance, step (the arm's), obstacle_step (the obstacles' index),
+        obstacle, first_violation (the arm's step), each [P][N]; no per_obstacle"""
+        o = self._obs(obstacles)
+        out = {"clearance": np.zeros((self.P, self.N))}
+        for k in ("step", "obstacle_step", "obstacle", "first_violation"):
+            out[k] = np.zeros((self.P, self.N), dtype=np.int32)
+        self._chk(self.L.pmaf_evaluate_paths_slack(self._h, _p(o), _pi(self._first(first)), float(margin), int(late), int(early),
+                                                   _p(out["clearance"]), _pi(out["step"]), _pi(out["obstacle_step"]),
+                                                   _pi(out["obstacle"]), _pi(out["first_violation"])))
+        return {k: self._sq(v) for k, v in out.items()}
+
+    def select_clear_slack(self, obstacles, margin, horizon, late=0, early=0, prev=None, adopt=False, first=None,
+                           skip_trailing=False):
+        """select_clear_tracked with the same timing slack (pmaf_select_clear_slack): the same dict"""
+        o = self._obs(obstacles)
+        pv = None if prev is None else np.ascontiguousarray(np.broadcast_to(np.asarray(prev, dtype=np.int32), (self.P,)))
+        out = {k: np.zeros(self.P, dtype=np.int32) for k in ("pick", "rule", "n_clear", "first_violation")}
+        out["cost"], out["clearance"] = np.zeros(self.P), np.zeros(self.P)
+        self._chk(self.L.pmaf_select_clear_slack(self._h, _p(o), _pi(self._first(first)), float(margin), int(horizon),
+                                                 1 if skip_trailing else 0, int(late), int(early), _pi(pv),
+                                                 1 if adopt else 0, _pi(out["pick"]), _pi(out["rule"]), _pi(out["n_clear"]),
+                                                 _p(out["cost"]), _p(out["clearance"]), _pi(out["first_violation"])))
         return {k: (v[0].item() if self.P == 1 else v) for k, v in out.items()}
 
     # -- joint selection on coupled handles (include/pmaf.h "joint selection on coupled handles") --
