@@ -6,6 +6,7 @@
 #                        policy 2 in two units: one-slot / multi-slot kernels, -DPMAF_W64_PART=1|2; policy 3 = the opt-in
 #                        contracted one, the only units compiled with -ffp-contract=fast). The step (rollout_w64_body) and
 #                        its dispatch live in the header pmaf_rollout_w64_body.hpp, which the two track units include too
+#                        (the text of one step in pmaf_rollout_w64_step.hpp: the body includes it once per step loop)
 #   pmaf_k_grp.hip   x3  the group rollout kernel (-DPMAF_GRP_MATH=0|2|3)
 #   pmaf_k_mw.hip    x3  the multi-wave-per-agent rollout kernel (62..256 obstacles at <= 1 wave per SIMD; -DPMAF_MW_MATH=1|2|3)
 #   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_xaudit_kernels.hpp) ... + the launch interface
@@ -101,7 +102,7 @@ KFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-m
 # PMAF_EXTRA_HFLAGS / PMAF_EXTRA_LDFLAGS: host objects / link line only (sanitizer builds: tools/asan.sh)
 HFLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -D__HIP_PLATFORM_AMD__ -I$ROCM/include ${PMAF_EXTRA_FLAGS} ${PMAF_EXTRA_HFLAGS}"
 
-DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_w64_body.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
+DEPS_K="pmaf_types.hpp pmaf_device.hpp pmaf_rollout_w64.hpp pmaf_rollout_w64_body.hpp pmaf_rollout_w64_step.hpp pmaf_rollout_grp.hpp pmaf_path_audit.hpp pmaf_xaudit_kernels.hpp pmaf_cross_audit.hpp pmaf_adopt.hpp"
 DEPS_TRACK="pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
 DEPS_FTRACK="pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
 DEPS_SELECT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_select_audit.hpp"   # ... and pmaf_k_select.hip

@@ -375,7 +375,13 @@ __device__ __forceinline__ V3 cv_close_threshold(const V3 cur, const bool keep, 
 // divide sequences -- is the same 32 instructions in all 64 lanes. It rides in idle lane NVL of the current vector's own
 // normalisation instead (v goes in for the lane's vector, the quotient is read back): same operations on the same
 // operand, one sequence less per step (round 4, last session: C2's Random agents 202.0 -> 190.8 us per rollout).
-template <int TILES, int TYPE, int MATH, bool PRE = false, bool DPPSUM = false, class KT = ExpK, int NVL = -1>
+// LONG (the one-slot DPP sum of the rollout kernels only; false: none of it): the step of the LONG loop of rollout_w64_body
+// (pmaf_rollout_w64_body.hpp), which a wave enters behind its first step with more than 16 terms (that step zeroes
+// *short_cap, the capacity in the short loop's guard, in the rare loop of the sum below) and never leaves. It adds the
+// list's SECOND chunk like the first, as sixteen separate statements in the block of the scaling chain, whatever the
+// count; chunk 1 is therefore cleared ahead of the compaction stores, which leaves every entry from `count` to 31 at
+// +0.0 (see there). Lists of more than 32 terms go on in a rare loop from the third chunk.
+template <int TILES, int TYPE, int MATH, bool PRE = false, bool DPPSUM = false, class KT = ExpK, int NVL = -1, bool LONG = false>
 __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double zv, V3 goal, V3 g, double dg, V3 gn,
                                                    const PopConst &C, double k_circ,
                                                    int n_obs, double *rot_g, unsigned &known_bits,
@@ -383,7 +389,9 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
                                                    V3 &F, double &scale, SecTimers &ST, const KT &EK,
                                                    const int rtype = 0,
                                                    const double s_pre = 0.0, const V3 ron_pre = V3{0.0, 0.0, 0.0},
-                                                   const lmask gate_m = ~0ull, const int32_t *cidx = nullptr) {
+                                                   const lmask gate_m = ~0ull, const int32_t *cidx = nullptr,
+                                                   int *short_cap = nullptr) {
+  static_assert(!LONG || (TILES == 1 && DPPSUM && TYPE != T_REAL), "the long loop belongs to the one-slot DPP sum of the rollout kernels");
   typedef Mth<MATH> MT;
   // TYPE == T_REAL: the heuristic is a run-time value (the real agent's step in
   // k_manager dispatches to the stored best agent's type, cf_agent.cpp:368-387)
@@ -482,6 +490,15 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   // the shell compute values that go to their scratch entry)
   int count = 0;
   double m_mid = 0.0;
+  if (LONG) {
+    // The long step adds chunk 1 unconditionally, and an earlier step may have left terms there (K = 25, then K = 3):
+    // every entry from `count` to 31 has to be +0.0, whatever was stored before. So every lane clears its double of
+    // chunk 1 HERE, ahead of this step's compaction stores (a wave's DS instructions execute in order: terms 16 ..
+    // count - 1 land on top of the zeros) -- one store per step, no condition on a count that is not known yet.
+    // Holds for count == 0 with terms discarded for zrv == 0, and for count == 16 and 32 (nothing / all of it rewritten).
+    wave_lds_fence();
+    clist[(16 << 2) + lane] = 0.0;
+  }
   // (two slots only: the four-slot kernel skips slots that hold nothing inside the shell, the last one included)
   constexpr bool MIN_MID = TILES == 2;
 #pragma unroll
@@ -562,6 +579,8 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
   if (DPPSUM) {
     // zero padding: the rest of the list's last chunk (the whole next chunk when the list ends on a chunk boundary)
     if ((lane & 15) >= (count & 15)) clist[((count >> 4) << 6) + lane] = 0.0;
+    // (LONG: with chunk 1 cleared in front of the compaction stores, see there, every entry from `count` to 31 is +0.0 now --
+    // for count < 16 the store above clears the rest of chunk 0, for 16 <= count < 32 the rest of chunk 1 once more)
   } else {  // zero padding behind the list (8 distinct entries, written by all lanes)
     double *e = clist + (size_t)(count + (lane % BATCH)) * 4;
     e[0] = 0.0; e[1] = 0.0; e[2] = 0.0;
@@ -713,6 +732,35 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
         PMAF_FM1(8) PMAF_FM1(9) PMAF_FM1(10) PMAF_FM1(11) PMAF_FM1(12) PMAF_FM1(13) PMAF_FM1(14) PMAF_FM1(15)
 #undef PMAF_FM1
       }
+      if constexpr (LONG) {
+        // the second chunk (fetched in front of the scaling chain) the same way, behind the first in the same block: the
+        // thirty-two accumulates are one dependent chain the scheduler threads through the scaling chain's. Hazards as
+        // above; the s_nop that covers a copy of the DPP source sits in ONE statement with the half's first accumulate,
+        // so nothing can come between them. Entries from `count` on are +0.0 (the padding above): exact.
+        double e2 = e_second;
+        asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(e2), "v"(one));
+#define PMAF_FM1(K) asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(e2), "v"(one));
+        PMAF_FM1(1) PMAF_FM1(2) PMAF_FM1(3) PMAF_FM1(4) PMAF_FM1(5) PMAF_FM1(6) PMAF_FM1(7)
+        PMAF_FM1(8) PMAF_FM1(9) PMAF_FM1(10) PMAF_FM1(11) PMAF_FM1(12) PMAF_FM1(13) PMAF_FM1(14) PMAF_FM1(15)
+#undef PMAF_FM1
+        asm volatile("s_nop 0" : "+v"(acc));   // (a v_readlane / the rare loop's DPP block reads acc next)
+        if (PMAF_SUM_TAIL_PIN) asm volatile("" : : "v"(sc), "v"(acc));
+        // more than 32 terms (rare here too): from the third chunk in the block form below, the successor's read in flight
+        if (PMAF_RARE(count > 32)) {
+          double e = clist[(32 << 2) + lane];
+          for (int c16 = 32; c16 < count; c16 += 16) {
+            const double en = clist[((c16 + 16) << 2) + lane];
+#define PMAF_FM(K) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
+            asm volatile("s_nop 4\n\t"
+                         PMAF_FM(0) PMAF_FM(1) PMAF_FM(2) PMAF_FM(3) PMAF_FM(4) PMAF_FM(5) PMAF_FM(6) PMAF_FM(7)
+                         PMAF_FM(8) PMAF_FM(9) PMAF_FM(10) PMAF_FM(11) PMAF_FM(12) PMAF_FM(13) PMAF_FM(14) PMAF_FM(15)
+                         "s_nop 1"
+                         : "+v"(acc) : "v"(e), "v"(one));
+#undef PMAF_FM
+            e = en;
+          }
+        }
+      } else {
       // (keeps the rest of the scaling chain in THIS block, in front of the rare loop: left alone the compiler sinks
       // it behind the loop, where it can no longer interleave with the 16 dependent adds)
       if (PMAF_SUM_TAIL_PIN) asm volatile("" : : "v"(sc), "v"(acc));
@@ -731,6 +779,11 @@ __device__ __forceinline__ void circ_and_scale_w64(int lane, V3 p, V3 v, double 
                      : "+v"(acc) : "v"(e), "v"(one));
 #undef PMAF_FM
         e = en;
+        // (rollout kernels: this was the short loop's last step, see LONG. The capacity its guard compares with lives
+        // in an SGPR of its own that only this block writes: the guard costs the common path what it always did. Opaque
+        // to the compiler, which otherwise recomputes the flag as `count > 16` on the common path -- 64-bit, so a VALU compare.)
+        if (short_cap) asm volatile("s_mov_b32 %0, 0" : "=s"(*short_cap));
+      }
       }
     }
     F = mk(readlane_d(acc, 0), readlane_d(acc, 16), readlane_d(acc, 32));
