@@ -10,8 +10,9 @@
 #   pmaf_k_grp.hip   x3  the group rollout kernel (-DPMAF_GRP_MATH=0|2|3)
 #   pmaf_k_mw.hip    x3  the multi-wave-per-agent rollout kernel (62..256 obstacles at <= 1 wave per SIMD; -DPMAF_MW_MATH=1|2|3)
 #   pmaf_k_misc.hip      generic rollout, manager, scoring, winner records, the path audit (pmaf_path_audit.hpp), the cross audit (pmaf_xaudit_kernels.hpp) ... + the launch interface
-#   pmaf_k_slack.hip     the cross audit with timing slack (k_cross_audit_slack; it shares the tile header
-#                        pmaf_cross_audit.hpp with the cross audit), a unit of its own so that the other units'
+#   pmaf_k_slack.hip     the cross audit with timing slack (k_cross_audit_slack: the band walk of the tile header
+#                        pmaf_cross_audit.hpp, which all four cross-audit kernels -- this one, k_cross_audit in
+#                        pmaf_k_misc.hip and the two attached units below -- include), a unit of its own so that the other units'
 #                        code objects do not move with it; its object is slack.o, outside the k_*.o set of twelve whose
 #                        disassembly tests/test_abi.py walks (tests/test_slack_audit.py holds it to the same: no scratch)
 #   pmaf_k_select.hip    the selection against the live list (pmaf_select_clear / pmaf_adopt_best), a unit of its own for
@@ -40,13 +41,14 @@
 #                        object fcouple.o
 #                        (tests/test_field_couple.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_xattach.hip   the cross audit on coupled handles (pmaf_cross_audit_attached / pmaf_select_pair_clear_tracked):
-#                        k_cross_audit_attached on the tile header pmaf_cross_audit.hpp, compiled with the plain kernel
+#                        k_cross_audit_attached, the step walk of the tile header pmaf_cross_audit.hpp over the terms of
+#                        pmaf_xattach_terms.hpp (device only; shared with the next unit), compiled with the plain kernel
 #                        flags (-ffp-contract=off: the riding sphere is one rounded multiply and one rounded add); a unit
 #                        of its own for the same reason, object xattach.o
 #                        (tests/test_attached_audit.py holds its kernel to no scratch through the resource record)
 #   pmaf_k_xattach_slack.hip the attached audit with timing slack (pmaf_cross_audit_attached_slack /
-#                        pmaf_select_pair_clear_tracked_slack): k_xaudit_attached_slack on the same tile header,
-#                        the attached audit's terms over the slacked audit's band, compiled with the plain kernel flags
+#                        pmaf_select_pair_clear_tracked_slack): k_xaudit_attached_slack, the same two headers: the
+#                        attached audit's terms over the tile header's band walk, compiled with the plain kernel flags
 #                        (-ffp-contract=off, as xattach.o); a unit of its own for the same reason, object xattach_slack.o
 #                        (tests/test_attached_slack_audit.py holds its kernel to no scratch through the resource record)
 #   pmaf_k_obslack.hip   the audits against the live list with timing slack (pmaf_evaluate_paths_slack /
@@ -107,8 +109,8 @@ DEPS_TRACK="pmaf_track.hpp"   # what pmaf_k_track.hip includes beside DEPS_K
 DEPS_FTRACK="pmaf_track.hpp pmaf_ftrack.hpp"   # ... and pmaf_k_ftrack.hip
 DEPS_SELECT="pmaf_track.hpp pmaf_ftrack.hpp pmaf_select_audit.hpp"   # ... and pmaf_k_select.hip
 DEPS_AUDITFT="$DEPS_SELECT pmaf_audit_chain.hpp pmaf_auditft.hpp pmaf_xattach.hpp"   # ... and pmaf_k_auditft.hip
-DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach.hip
-DEPS_XATTACH_SLACK="pmaf_ftrack.hpp pmaf_xattach.hpp"   # ... and pmaf_k_xattach_slack.hip
+DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp pmaf_xattach_terms.hpp"   # ... and pmaf_k_xattach.hip
+DEPS_XATTACH_SLACK="pmaf_ftrack.hpp pmaf_xattach.hpp pmaf_xattach_terms.hpp"   # ... and pmaf_k_xattach_slack.hip
 DEPS_OBSLACK="$DEPS_SELECT pmaf_obstacle_slack.hpp"   # ... and pmaf_k_obslack.hip
 DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt

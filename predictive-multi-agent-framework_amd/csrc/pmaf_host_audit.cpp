@@ -486,6 +486,21 @@ static XAttachSide attach_side(const pmaf_planner *h, const XAuditAttach &T, int
   return XAttachSide{f.d_src.get() + (size_t)p * PMAF_FTRACK_LANES, f.d_scale.get() + (size_t)p * PMAF_FTRACK_LANES,
                      f.d_anchor.get() + (size_t)p * 3 * PMAF_FTRACK_LANES, rad};
 }
+// the attached kernels' arguments: the cross audit's X and the two populations' terms; sphere: where the call's sphere
+// matrix lies in the scratch (XAuditAttach above)
+static CrossAuditAttachedArgs attached_args(const pmaf_planner *h, const CrossAuditArgs &X, const XAuditAttach &att,
+                                            int32_t *sphere) {
+  CrossAuditAttachedArgs T{};
+  T.X = X;
+  T.a = attach_side(h, att, att.pop_a);
+  T.b = attach_side(h, att, att.pop_b);
+  T.pop_a = att.pop_a;
+  T.pop_b = att.pop_b;
+  T.M = h->D.n_obs - 1;
+  T.radius = h->D.C.rad;
+  T.sphere = att.want_sphere ? sphere : nullptr;
+  return T;
+}
 
 // the launch: set A against set B into the scratch, the step matrices where they are wanted. Four kernels: step against
 // step or slacked, each with or without the attached terms
@@ -521,15 +536,7 @@ static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *pat
   A.step = want_a ? B.step : nullptr;
   if (slack && att) {   // the attached audit's terms over the slacked audit's band
     CrossAuditAttachedSlackArgs U{};
-    CrossAuditAttachedArgs &T = U.T;
-    T.X = A;
-    T.a = attach_side(h, *att, att->pop_a);
-    T.b = attach_side(h, *att, att->pop_b);
-    T.pop_a = att->pop_a;
-    T.pop_b = att->pop_b;
-    T.M = h->D.n_obs - 1;
-    T.radius = h->D.C.rad;
-    T.sphere = att->want_sphere ? B.sphere : nullptr;
+    U.T = attached_args(h, A, *att, B.sphere);
     U.late_a = slack->late_a;
     U.late_b = slack->late_b;
     U.step_b = want_b ? B.step_b : nullptr;
@@ -540,16 +547,7 @@ static void xaudit_launch(pmaf_planner *h, const XAuditBuf &B, const double *pat
     S.step_b = want_b ? B.step_b : nullptr;
     pmaf_k_launch_cross_audit_slack(S, h->stream);
   } else if (att) {
-    CrossAuditAttachedArgs T{};
-    T.X = A;
-    T.a = attach_side(h, *att, att->pop_a);
-    T.b = attach_side(h, *att, att->pop_b);
-    T.pop_a = att->pop_a;
-    T.pop_b = att->pop_b;
-    T.M = h->D.n_obs - 1;
-    T.radius = h->D.C.rad;
-    T.sphere = att->want_sphere ? B.step_b : nullptr;
-    pmaf_k_launch_cross_audit_attached(T, h->stream);
+    pmaf_k_launch_cross_audit_attached(attached_args(h, A, *att, B.step_b), h->stream);
   } else {
     pmaf_k_launch_cross_audit(A, h->stream);
   }
@@ -647,21 +645,29 @@ int pmaf_cross_audit(pmaf_planner *h, int32_t pop_a, int32_t pop_b, double separ
   });
 }
 
+// what pmaf_cross_audit_attached and its slacked form do before the audit: the arguments' validation (all of it before any
+// wait), then the list staged on the device behind the running rollout
+static XAuditAttach attached_prologue(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
+                                      XAuditSlack *slack, const double *clearance, bool want_sphere, const char *who) {
+  REQUIRE(h && obstacles && clearance, std::string(who) + ": NULL argument");
+  const DevView &D = h->D;
+  if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
+    fail(PMAF_ERR_INVALID, std::string(who) + ": need two different populations of the handle");
+  check_range(&separation, 1, "separation");
+  clamp_slack(h, slack, who);
+  check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
+  h->use_device();
+  sync(h);   // behind the running rollout; the list's upload below is in stream order behind it
+  return XAuditAttach{pop_a, pop_b, upload_plan_obstacles(h, obstacles), want_sphere};
+}
+
 int pmaf_cross_audit_attached(pmaf_planner *h, int32_t pop_a, int32_t pop_b, const double *obstacles, double separation,
                               double *clearance, int32_t *step, int32_t *sphere) {
   return guarded([&] {
-    REQUIRE(h && obstacles && clearance, "pmaf_cross_audit_attached: NULL argument");
-    const DevView &D = h->D;
-    if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
-      fail(PMAF_ERR_INVALID, "pmaf_cross_audit_attached: need two different populations of the handle");
-    check_range(&separation, 1, "separation");
-    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
-    h->use_device();
-    sync(h);   // behind the running rollout; the list's upload below is in stream order behind it
-    const XAuditAttach T{pop_a, pop_b, upload_plan_obstacles(h, obstacles), sphere != nullptr};
-    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, step != nullptr, false,
-                                                "pmaf_cross_audit_attached", nullptr, &T);
-    xaudit_download(h, B, (size_t)D.N * D.N, clearance, step, sphere);
+    const char *who = "pmaf_cross_audit_attached";
+    const XAuditAttach T = attached_prologue(h, pop_a, pop_b, obstacles, separation, nullptr, clearance, sphere != nullptr, who);
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, nullptr, step != nullptr, false, who, nullptr, &T);
+    xaudit_download(h, B, (size_t)h->D.N * h->D.N, clearance, step, sphere);   // (the sphere matrix lies in the step_b part)
   });
 }
 
@@ -669,20 +675,12 @@ int pmaf_cross_audit_attached_slack(pmaf_planner *h, int32_t pop_a, int32_t pop_
                                     int32_t late_a, int32_t late_b, double *clearance, int32_t *step_a, int32_t *step_b,
                                     int32_t *sphere) {
   return guarded([&] {
-    REQUIRE(h && obstacles && clearance, "pmaf_cross_audit_attached_slack: NULL argument");
-    const DevView &D = h->D;
-    if (pop_a < 0 || pop_a >= D.P || pop_b < 0 || pop_b >= D.P || pop_a == pop_b)
-      fail(PMAF_ERR_INVALID, "pmaf_cross_audit_attached_slack: need two different populations of the handle");
-    check_range(&separation, 1, "separation");
+    const char *who = "pmaf_cross_audit_attached_slack";
     XAuditSlack slack{late_a, late_b};
-    clamp_slack(h, &slack, "pmaf_cross_audit_attached_slack");
-    check_range(obstacles, (size_t)D.P * D.n_obs * 7, "obstacles");
-    h->use_device();
-    sync(h);   // behind the running rollout; the list's upload below is in stream order behind it
-    const XAuditAttach T{pop_a, pop_b, upload_plan_obstacles(h, obstacles), sphere != nullptr};
-    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, &slack, step_a != nullptr, step_b != nullptr,
-                                                "pmaf_cross_audit_attached_slack", nullptr, &T);
-    xaudit_download(h, B, (size_t)D.N * D.N, clearance, step_a, step_b, sphere);
+    const XAuditAttach T = attached_prologue(h, pop_a, pop_b, obstacles, separation, &slack, clearance, sphere != nullptr, who);
+    const XAuditBuf B = cross_audit_populations(h, pop_a, pop_b, separation, &slack, step_a != nullptr, step_b != nullptr, who,
+                                                nullptr, &T);
+    xaudit_download(h, B, (size_t)h->D.N * h->D.N, clearance, step_a, step_b, sphere);
   });
 }
 

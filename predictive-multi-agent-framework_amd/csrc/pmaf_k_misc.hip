@@ -978,8 +978,7 @@ void pmaf_k_launch_path_audit_only(const DevView &D, const AuditArgs &A, hipStre
 }
 
 void pmaf_k_launch_cross_audit(const CrossAuditArgs &A, hipStream_t s) {
-  const dim3 grid((unsigned)((A.n_b + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE), (unsigned)((A.n_a + PMAF_XAUDIT_TILE - 1) / PMAF_XAUDIT_TILE));
-  hipLaunchKernelGGL(k_cross_audit, grid, dim3(PMAF_XAUDIT_THREADS), 0, s, A);
+  hipLaunchKernelGGL(k_cross_audit, xaudit_grid(A), dim3(PMAF_XAUDIT_THREADS), 0, s, A);
 }
 
 void pmaf_k_launch_pair_reduce(const PairArgs &A, hipStream_t s) {

@@ -2,7 +2,8 @@
 // pmaf_cross_audit_attached, pmaf_select_pair_clear_tracked, and their slacked forms): the structs and the launch interface
 // between pmaf_host_audit.cpp and the kernels the calls add -- k_cross_audit_attached (pmaf_k_xattach.hip),
 // k_xaudit_attached_slack (pmaf_k_xattach_slack.hip) and k_ft_masked_audit (pmaf_k_auditft.hip). A header of its own so that no other kernel unit's inputs change with it:
-// CrossAuditArgs, SelectArgs and FTrackArgs stay what they are.
+// CrossAuditArgs, SelectArgs and FTrackArgs stay what they are. Read by the host compiler too: the device code of the terms
+// is in pmaf_xattach_terms.hpp.
 #pragma once
 #include "pmaf_types.hpp"
 #include "pmaf_ftrack.hpp"

@@ -16,9 +16,8 @@
 //                 pair-step, so it is blocked like a small GEMM over the tile of pmaf_cross_audit.hpp (ownership, LDS
 //                 layout, staging and the hold rule are described there): both tiles' chunk is staged into LDS and a
 //                 thread keeps one running (d2, k) for each of its 2 x 2 pairs -- 12 LDS reads for 4 pair-steps instead
-//                 of 24 global ones.
-//                  - steps past a pair's K (the block walks to the longest path of its tile) and past the ragged end of
-//                    the last chunk repeat a held point, tie with an earlier step and so never win the strict `<`.
+//                 of 24 global ones. The loop is that header's xaudit_step_walk on the points as they lie (why a step
+//                 past a pair's K never wins is said there).
 //                  - 2 x 2 pairs x (d2, k) + 12 staged values: a small register block (resource report: no scratch),
 //                    several waves per SIMD.
 // k_pair_reduce   pmaf_select_pair: over the device-resident matrix and the two cost vectors, the minimum of
@@ -45,32 +44,7 @@ __global__ __launch_bounds__(PMAF_XAUDIT_THREADS) void k_cross_audit(CrossAuditA
   const double inf = __builtin_huge_val();
   double best[2][2] = {{inf, inf}, {inf, inf}};
   int bk[2][2] = {{-1, -1}, {-1, -1}};
-  for (int k0 = 0; k0 < K; k0 += C) {   // block-uniform trip count
-    xaudit_stage(s_a, A.paths_a, s_na, a0, A.n_a, A.cap, k0);
-    xaudit_stage(s_b, A.paths_b, s_nb, b0, A.n_b, A.cap, k0);
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < C; k++) {
-      const double *ra = s_a + k * 3 * TP + ty, *rb = s_b + k * 3 * TP + tx;
-      V3 x[2], y[2];
-#pragma unroll
-      for (int r = 0; r < 2; r++) {
-        x[r] = mk(ra[16 * r], ra[TP + 16 * r], ra[2 * TP + 16 * r]);
-        y[r] = mk(rb[16 * r], rb[TP + 16 * r], rb[2 * TP + 16 * r]);
-      }
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-          const V3 d = x[r] - y[c];
-          const double d2 = dot(d, d);
-          const bool take = d2 < best[r][c];   // strict, k ascending: ties keep the smallest k, a NaN never wins
-          best[r][c] = take ? d2 : best[r][c];
-          bk[r][c] = take ? k0 + k : bk[r][c];
-        }
-    }
-    __syncthreads();
-  }
+  xaudit_step_walk(A, a0, b0, K, s_a, s_b, s_na, s_nb, tx, ty, XAuditAsLies{}, XAuditAsLies{}, best, bk);
 #pragma unroll
   for (int r = 0; r < 2; r++)
 #pragma unroll
