@@ -846,6 +846,25 @@ class CfManager {
     }
   }
 
+  // ... from memory the device reads: the output of a predictor on the same GPU, taken where it lies
+  // (pmaf_set_obstacle_tracks_device, include/pmaf.h "obstacle tracks from device memory"). d_tracks: [len][M][components]
+  // elements of `dtype` (PMAF_TRACK_F64 / PMAF_TRACK_F32), densely packed; components 6 = position and velocity verbatim,
+  // 3 = positions, the velocities their forward differences over the rollout step. producer_stream: the hipStream_t the
+  // tracks were written on (the ingest waits for it on the device), or nullptr when they are complete. len == 0
+  // detaches (d_tracks must still not be null). The values are range-checked on the device: the std::runtime_error of a
+  // refusal names the first offender, and the tracks attached before stay. The exceptions are setObstacleTracks'.
+  void setObstacleTracksDevice(const void *d_tracks, int len, int components, int dtype, void *producer_stream = nullptr,
+                               int first = 0) {
+    require();
+    const int32_t n = len;
+    check(pmaf_set_obstacle_tracks_device(h_, d_tracks, &n, n > 0 ? n : 1, components, dtype, producer_stream),
+          "setObstacleTracksDevice");
+    if (n > 0 && first != 0) {
+      const int32_t f = first;
+      check(pmaf_set_obstacle_track_offset(h_, &f), "setObstacleTracksDevice");
+    }
+  }
+
   // A closed loop that keeps following the same prediction: the tracks' offset moves on by `by` points (one per tick)
   // without another upload (pmaf_set_obstacle_track_offset).
   void advanceObstacleTracks(int by = 1) {

@@ -594,7 +594,9 @@ int pmaf_get_repulsive_track(pmaf_planner *h, double *track, int32_t *len, int32
  *   len == NULL or every len == 0 detaches. A value inside len that is NaN or outside the supported numeric range,
  *   len < 0 or len > max_len: PMAF_ERR_INVALID. Waits for a running rollout as the setters do; the upload runs in
  *   stream order on the handle's stream into a grow-only device buffer (transposed on the host so that a wave's load
- *   of one component is contiguous).
+ *   of one component is contiguous). Tracks that already lie in device memory -- a predictor's output on the same
+ *   GPU, float64 or float32, with or without velocities -- go in through pmaf_set_obstacle_tracks_device (further
+ *   below) without the trip through the host.
  * pmaf_set_obstacle_track_offset: first [P], each >= 0 (PMAF_ERR_INVALID otherwise): a closed loop that advances
  *   along the same prediction by one point per tick uploads P integers instead of the tracks. PMAF_ERR_STATE while no
  *   tracks are attached.
@@ -651,6 +653,56 @@ int pmaf_set_obstacle_track_offset(pmaf_planner *h, const int32_t *first);
 int pmaf_get_obstacle_tracks(pmaf_planner *h, double *tracks, int32_t *len, int32_t *first, int32_t max_len);
 int pmaf_couple_obstacle_tracks(pmaf_planner *h, const int32_t *src_pop /* [P][M] */, const double *scale /* [P][M] */,
                                 const double *anchor /* [P][M][3] */, int32_t shift);
+
+/* ---- obstacle tracks from device memory: a predictor on the same device feeds the rollouts (export added under ABI 7) ----
+ * pmaf_set_obstacle_tracks takes host memory: a motion predictor that runs on the handle's device would read its output
+ * back, widen it to double, invent velocities it may not have, and upload it again, every tick. This call takes the
+ * tracks where they lie. Everything it does not restate below is pmaf_set_obstacle_tracks: effect from the next
+ * pmaf_start / pmaf_tick until replaced, every offset becomes 0, the route rule and its message (PMAF_ERR_STATE off the
+ * one-slot wave-per-agent kernel of the default policy), the coupled-handle rules (a coupled population needs len == 0;
+ * the uncoupled populations of a coupled handle are replaced one at a time; a buffer that must grow keeps what it holds;
+ * stride max(upload max_len, max_prediction_steps)), columns >= M zero, every len == 0 detaches, tracks are inputs and
+ * not checkpoint state, and pmaf_get_obstacle_tracks returns the ingested points -- with components == 3 the derived
+ * velocities too. Detaching with NULL stays the host call's business: pmaf_set_obstacle_tracks(h, NULL, NULL, 0).
+ * Source. d_tracks: memory the handle's device can read (device memory of that device, of a peer device with peer
+ *   access, pinned or managed host memory), [P][max_len][M][components] elements of `dtype`, densely packed,
+ *   M = n_obstacles - 1. Of population p exactly the leading len[p] * M * components elements of its slab are read; what
+ *   lies in the padding up to max_len is neither read nor validated (as in the host call). Alignment is the element's
+ *   own, 8 bytes for PMAF_TRACK_F64 and 4 for PMAF_TRACK_F32 (less: PMAF_ERR_INVALID); a source that is 8-aligned but not
+ *   16-aligned is legal. len stays a HOST array of P integers.
+ * components == 6: position and velocity, taken verbatim: PMAF_TRACK_F32 is widened to double exactly, the bit pattern
+ *   of a PMAF_TRACK_F64 value is preserved (-0.0 included) -- with F64 this is pmaf_set_obstacle_tracks on the same
+ *   numbers, bit for bit.
+ * components == 3: positions only, taken as above (F32 widened first; differences and quotients in double). The
+ *   velocity of point k < len - 1 is u_k = RN(RN(x_{k+1} - x_k) / dt) per component, dt the handle's rollout step, the
+ *   division the correctly rounded one, no contraction; +0.0 at point len - 1, which the rollout holds: a held obstacle
+ *   rests. (The composed tracks' velocity rule of pmaf_couple_obstacle_tracks, for uploaded positions.)
+ * Validation, on the device: every ingested value -- after widening, and with components == 3 every derived velocity
+ *   as well -- is finite and either 0 or 2^-100 <= |x| <= 2^100 (an F32 subnormal is refused, and dt == 0 refuses
+ *   itself). A violation is PMAF_ERR_INVALID with a message that names population, point, obstacle and component (0 .. 2
+ *   position, 3 .. 5 velocity) of the FIRST offender in source order, decided by a minimum over a flat index: a derived
+ *   velocity counts at its point, behind its obstacle's positions, and is judged only where both positions it is taken
+ *   from pass themselves (an out-of-range position is named itself, not through the difference it spoils). A refused
+ *   call changes nothing: tracks, lengths, offsets and route stay, pmaf_get_obstacle_tracks returns what it returned.
+ * Other arguments. d_tracks == NULL, len == NULL, max_len < 1, len[p] outside [0, max_len], components not 3 or 6, an
+ *   unknown dtype: PMAF_ERR_INVALID. The pointer is classified before anything is enqueued (hipPointerGetAttributes):
+ *   pageable host memory and another device's memory without peer access are PMAF_ERR_INVALID (enabling peer access is
+ *   the caller's: the call leaves the process's device state as it finds it), and so is, where the runtime can tell
+ *   (hipMemGetAddressRange), a source whose last element to be read lies outside its allocation.
+ * Ordering. producer_stream != NULL (a hipStream_t of the handle's device): the ingest waits for everything enqueued on
+ *   that stream up to the call -- an event recorded there, awaited by the handle's stream; the producer is never
+ *   synchronised with the host. NULL: the caller vouches that the data is complete, or produced it on pmaf_stream(h).
+ *   Waits for a running rollout as the setters do (it still reads the buffer), refuses an abandoned tick as they do,
+ *   and returns after the ingest has finished: the source may be overwritten on return, and there is one set of tracks.
+ * Cost. Two small kernels per call (k_ftingest_check, k_ftingest_store: the second returns at once behind a refusal)
+ *   and one 8-byte copy for the verdict; a handle that never calls this launches exactly what it launched before.
+ * Out of scope: a device source for the repulsive track and for the live obstacle list; an asynchronous form whose
+ *   verdict arrives at the next launch; tracks on the routes that refuse them (Limits above). */
+#define PMAF_TRACK_F64 0
+#define PMAF_TRACK_F32 1
+int pmaf_set_obstacle_tracks_device(pmaf_planner *h, const void *d_tracks, const int32_t *len /* host, [P] */,
+                                    int32_t max_len, int32_t components /* 6 or 3 */, int32_t dtype,
+                                    void *producer_stream /* hipStream_t, or NULL */);
 
 /* ---- audits against the obstacle tracks: the path audit and the clear selection where the rollouts saw the field
  * obstacles (exports added under ABI 7) ----

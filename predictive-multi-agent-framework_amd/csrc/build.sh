@@ -40,6 +40,11 @@
 #                        position is one rounded multiply and one rounded add); a unit of its own for the same reason,
 #                        object fcouple.o
 #                        (tests/test_field_couple.py holds its kernels to no scratch through the resource record)
+#   pmaf_k_ftingest.hip  the obstacle tracks' device-memory source (pmaf_set_obstacle_tracks_device): k_ftingest_check and
+#                        k_ftingest_store, each for double | float elements and 6 | 3 components, compiled with the plain
+#                        kernel flags (-ffp-contract=off, as fcouple.o: the derived velocity is one rounded difference
+#                        and one rounded quotient); a unit of its own for the same reason, object ftingest.o
+#                        (tests/test_track_ingest.py holds its kernels to no scratch through the resource record)
 #   pmaf_k_xattach.hip   the cross audit on coupled handles (pmaf_cross_audit_attached / pmaf_select_pair_clear_tracked):
 #                        k_cross_audit_attached, the step walk of the tile header pmaf_cross_audit.hpp over the terms of
 #                        pmaf_xattach_terms.hpp (device only; shared with the next unit), compiled with the plain kernel
@@ -113,6 +118,7 @@ DEPS_XATTACH="pmaf_ftrack.hpp pmaf_xattach.hpp pmaf_xattach_terms.hpp"   # ... a
 DEPS_XATTACH_SLACK="pmaf_ftrack.hpp pmaf_xattach.hpp pmaf_xattach_terms.hpp"   # ... and pmaf_k_xattach_slack.hip
 DEPS_OBSLACK="$DEPS_SELECT pmaf_obstacle_slack.hpp"   # ... and pmaf_k_obslack.hip
 DEPS_FCOUPLE="pmaf_track.hpp pmaf_ftrack.hpp pmaf_fcouple.hpp"   # ... and pmaf_k_fcouple.hip
+DEPS_FTINGEST="pmaf_track.hpp pmaf_ftrack.hpp pmaf_ftingest.hpp ../../include/pmaf.h"   # ... and pmaf_k_ftingest.hip
 # the objects of an output directory belong to ONE set of flags: a directory built with other flags is rebuilt
 STAMP="$KFLAGS | $HFLAGS | $PMAF_EXTRA_LDFLAGS"
 FLAGS_CHANGED=0
@@ -130,6 +136,7 @@ kcompile() {  # kcompile <object stem> <source> [defines...]
   [ "$src" = pmaf_k_select.hip ] && extra=$DEPS_SELECT
   [ "$src" = pmaf_k_auditft.hip ] && extra=$DEPS_AUDITFT
   [ "$src" = pmaf_k_fcouple.hip ] && extra=$DEPS_FCOUPLE
+  [ "$src" = pmaf_k_ftingest.hip ] && extra=$DEPS_FTINGEST
   [ "$src" = pmaf_k_obslack.hip ] && extra=$DEPS_OBSLACK
   [ "$src" = pmaf_k_xattach.hip ] && extra=$DEPS_XATTACH
   [ "$src" = pmaf_k_xattach_slack.hip ] && extra=$DEPS_XATTACH_SLACK
@@ -168,6 +175,7 @@ kcompile pairclear pmaf_k_pairclear.hip
 kcompile auditft pmaf_k_auditft.hip
 kcompile dbgmath pmaf_k_dbgmath.hip
 kcompile fcouple pmaf_k_fcouple.hip
+kcompile ftingest pmaf_k_ftingest.hip
 kcompile xattach pmaf_k_xattach.hip
 kcompile xattach_slack pmaf_k_xattach_slack.hip
 kcompile obslack pmaf_k_obslack.hip
@@ -187,8 +195,8 @@ done
 printf '%s' "$STAMP" > "$OBJ/flags.txt"
 for n in "${names[@]}"; do grep -E -A3 "warning:|error:" "$OBJ/$n.log" >&2 || true; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpmaf_hip.so" \
-  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o "$OBJ"/xattach.o "$OBJ"/xattach_slack.o "$OBJ"/obslack.o \
+  "$OBJ"/k_w64_m2_t1.o "$OBJ"/k_w64_m2_tn.o "$OBJ"/k_w64_m0.o "$OBJ"/k_w64_m1.o "$OBJ"/k_grp_m2.o "$OBJ"/k_grp_m0.o "$OBJ"/k_w64_m3.o "$OBJ"/k_grp_m3.o "$OBJ"/k_mw_m1.o "$OBJ"/k_mw_m2.o "$OBJ"/k_mw_m3.o "$OBJ"/k_misc.o "$OBJ"/slack.o "$OBJ"/dbgmath.o "$OBJ"/select.o "$OBJ"/pairclear.o "$OBJ"/track.o "$OBJ"/ftrack.o "$OBJ"/auditft.o "$OBJ"/fcouple.o "$OBJ"/ftingest.o "$OBJ"/xattach.o "$OBJ"/xattach_slack.o "$OBJ"/obslack.o \
   $(for u in $HOST_UNITS; do echo "$OBJ/$u.o"; done) -L"$ROCM/lib" -lrccl -Wl,-rpath,"$ROCM/lib" ${PMAF_EXTRA_LDFLAGS}
 # (the log of an object that was up to date is the one of its last compile)
-cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log "$OBJ"/xattach.log "$OBJ"/xattach_slack.log "$OBJ"/obslack.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
+cat "$OBJ"/k_*.log "$OBJ"/slack.log "$OBJ"/dbgmath.log "$OBJ"/select.log "$OBJ"/pairclear.log "$OBJ"/track.log "$OBJ"/ftrack.log "$OBJ"/auditft.log "$OBJ"/fcouple.log "$OBJ"/ftingest.log "$OBJ"/xattach.log "$OBJ"/xattach_slack.log "$OBJ"/obslack.log | grep "kernel-resource-usage" | sed -e 's/^[^ ]* remark: *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' > "$OUT/resource_usage.txt"
 echo "built $OUT/libpmaf_hip.so"

@@ -3,6 +3,8 @@
 // interface: pmaf_types.hpp). The path audit and the selections: pmaf_host_audit.cpp; the winner-record exchange and
 // the peer mailboxes: pmaf_host_exchange.cpp; checkpointing: pmaf_host_state.cpp (shared: pmaf_host_impl.hpp).
 // Plain C++ against the HIP runtime API; there is no CPU fallback in this library.
+#include <functional>
+
 #include "pmaf_host_impl.hpp"
 
 static thread_local std::string g_err;
@@ -707,13 +709,16 @@ int pmaf_start(pmaf_planner *h) {
 
 // ---- repulsive track ----
 // attach / detach: the route's `tracked` input follows, and an attach the routed launch cannot carry is refused here
+// (check_tracked: the refusal alone, for a call that may still refuse for another reason before it attaches)
+static void check_tracked(const pmaf_planner *h, const char *who, TrackKind kind) {
+  bool pmaf_route::Input::*flag = (kind == FIELD_TRACKS) ? &pmaf_route::Input::field_tracked : &pmaf_route::Input::tracked;
+  pmaf_route::Input in = h->route_in;
+  in.*flag = true;
+  require_track_route(h, pmaf_route::route(in), who, kind);
+}
 static void set_tracked(pmaf_planner *h, bool want, const char *who, TrackKind kind = REPULSIVE_TRACK) {
   bool pmaf_route::Input::*flag = (kind == FIELD_TRACKS) ? &pmaf_route::Input::field_tracked : &pmaf_route::Input::tracked;
-  if (want) {
-    pmaf_route::Input in = h->route_in;
-    in.*flag = true;
-    require_track_route(h, pmaf_route::route(in), who, kind);
-  }
+  if (want) check_tracked(h, who, kind);
   h->route_in.*flag = want;
   reroute(h);
 }
@@ -819,25 +824,76 @@ static void reserve_ftrack_aux(pmaf_planner *h) {
 
 // Grow the points' buffer to `need` points per population and KEEP what it holds (the host has no copy of the points): a
 // coupled handle's buffer is shared between the composed populations and the uploaded ones, and either side may outgrow
-// it while the other's points are still followed. The caller has drained the stream.
+// it while the other's points are still followed. The caller has drained the stream. The points stay on the device: the
+// larger buffer is zeroed and filled beside the old one, one copy per population to its new stride, and then takes its
+// place (a failed allocation leaves the old buffer and its stride as they were).
 static void grow_ftrack_keeping(pmaf_planner *h, int need) {
   pmaf_planner::FieldTrack &f = h->ftrk;
   const int P = h->D.P, old = f.stride;
   if (f.d_pts.get() && need <= old) return;
-  std::vector<double> was;
-  if (f.d_pts.get() && old > 0) {
-    was.resize((size_t)P * old * PMAF_FTRACK_POINT);
-    h->download(was.data(), f.d_pts.get(), was.size());
-  }
-  f.stride = 0;   // (a failed allocation leaves an empty buffer)
-  f.d_pts.reserve(sizeof(double) * (size_t)P * need * PMAF_FTRACK_POINT);
-  f.stride = need;
-  std::vector<double> pts((size_t)P * need * PMAF_FTRACK_POINT, 0.0);
-  if (!was.empty())
+  DeviceBuf<double> grown;
+  const size_t bytes = sizeof(double) * (size_t)P * need * PMAF_FTRACK_POINT;
+  grown.reserve(bytes);
+  HIP_CHECK(hipMemsetAsync(grown.get(), 0, bytes, h->stream));
+  if (f.d_pts.get() && old > 0)
     for (int p = 0; p < P; p++)
-      std::memcpy(pts.data() + (size_t)p * need * PMAF_FTRACK_POINT, was.data() + (size_t)p * old * PMAF_FTRACK_POINT,
-                  sizeof(double) * (size_t)old * PMAF_FTRACK_POINT);
-  h->upload(f.d_pts.get(), pts.data(), pts.size());
+      HIP_CHECK(hipMemcpyAsync(grown.get() + (size_t)p * need * PMAF_FTRACK_POINT, f.d_pts.get() + (size_t)p * old * PMAF_FTRACK_POINT,
+                               sizeof(double) * (size_t)old * PMAF_FTRACK_POINT, hipMemcpyDeviceToDevice, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  f.d_pts.swap(grown);
+  f.stride = need;
+}
+
+// The caller's lengths, as every setter of uploaded obstacle tracks holds them: inside [0, max_len], 0 for a coupled
+// population; per_pop(p) is the setter's own look at population p's values, at the place of the loop where the host
+// call has it. Returns whether any population has points.
+static bool ftrack_lens(pmaf_planner *h, const int32_t *len, int32_t max_len, const std::string &who,
+                        const std::function<void(int)> &per_pop) {
+  const pmaf_planner::FieldTrack &f = h->ftrk;
+  bool any = false;
+  REQUIRE(max_len >= 1, who + ": max_len must be >= 1");
+  for (int p = 0; p < h->D.P; p++) {
+    REQUIRE(len[p] >= 0 && len[p] <= max_len, who + ": need 0 <= len <= max_len");
+    REQUIRE(len[p] == 0 || !f.is_coupled(p), who + ": the population's tracks come from pmaf_couple_obstacle_tracks (len must be 0)");
+    per_pop(p);
+    any = any || len[p] > 0;
+  }
+  return any;
+}
+
+// What a setter books once its points are accepted: attached, the lengths (len == NULL: none), every offset 0 ...
+static void book_ftrack_lens(pmaf_planner *h, const int32_t *len) {
+  pmaf_planner::FieldTrack &f = h->ftrk;
+  const int P = h->D.P;
+  f.attached = len != nullptr;
+  f.first.assign(P, 0);
+  f.len.assign(P, 0);
+  for (int p = 0; p < P && len; p++) f.len[p] = len[p];
+}
+// ... and their device copies: the coupled populations' len and first are the device's (k_fcouple_compose), the others'
+// are replaced one population at a time
+static void upload_ftrack_lens(pmaf_planner *h) {
+  pmaf_planner::FieldTrack &f = h->ftrk;
+  const int P = h->D.P;
+  // (one wait for all of them: the host copies are the handle's own and outlive it)
+  if (!f.coupled) {
+    HIP_CHECK(hipMemcpyAsync(f.d_len.get(), f.len.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(f.d_first.get(), f.first.data(), sizeof(int32_t) * P, hipMemcpyHostToDevice, h->stream));
+  } else {
+    for (int p = 0; p < P; p++) {
+      if (f.is_coupled(p)) continue;
+      HIP_CHECK(hipMemcpyAsync(f.d_len.get() + p, &f.len[p], sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(hipMemcpyAsync(f.d_first.get() + p, &f.first[p], sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+// every len == 0 (or no tracks given): the uploaded tracks go, a coupling stays. The caller has drained the stream.
+static void detach_uploaded_ftracks(pmaf_planner *h, const char *who) {
+  pmaf_planner::FieldTrack &f = h->ftrk;
+  book_ftrack_lens(h, nullptr);
+  if (!f.coupled) set_tracked(h, false, who, FIELD_TRACKS);
+  if (f.d_len.get()) upload_ftrack_lens(h);   // (the getter reads them)
 }
 
 int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_t *len, int32_t max_len) {
@@ -848,53 +904,36 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
     pmaf_planner::FieldTrack &f = h->ftrk;
     const int P = h->D.P, M = h->D.n_obs - 1;
     bool any = false;
-    if (tracks && len) {
-      REQUIRE(max_len >= 1, "pmaf_set_obstacle_tracks: max_len must be >= 1");
-      for (int p = 0; p < P; p++) {
-        REQUIRE(len[p] >= 0 && len[p] <= max_len, "pmaf_set_obstacle_tracks: need 0 <= len <= max_len");
-        REQUIRE(len[p] == 0 || !f.is_coupled(p), "pmaf_set_obstacle_tracks: the population's tracks come from pmaf_couple_obstacle_tracks (len must be 0)");
+    if (tracks && len)
+      any = ftrack_lens(h, len, max_len, "pmaf_set_obstacle_tracks", [&](int p) {
         check_range(tracks + (size_t)p * max_len * M * 6, (size_t)len[p] * M * 6, "pmaf_set_obstacle_tracks: tracks");
-        any = any || len[p] > 0;
-      }
-    }
+      });
     if (any) set_tracked(h, true, "pmaf_set_obstacle_tracks", FIELD_TRACKS);
     sync(h);   // a running rollout still reads the buffers
-    f.attached = any;
-    f.first.assign(P, 0);
-    f.len.assign(P, 0);
+    if (!any) {
+      detach_uploaded_ftracks(h, "pmaf_set_obstacle_tracks");
+      return;
+    }
+    book_ftrack_lens(h, len);
     if (f.coupled) {
       // the coupled populations' points, len and first are the device's (k_fcouple_compose): the others' are replaced one
       // population at a time, and a buffer that has to grow keeps what it holds
-      for (int p = 0; p < P && any; p++) f.len[p] = len[p];
-      if (any) grow_ftrack_keeping(h, (int)max_len);
+      grow_ftrack_keeping(h, (int)max_len);
       std::vector<double> pts((size_t)f.stride * PMAF_FTRACK_POINT);
-      const int32_t zero = 0;
       for (int p = 0; p < P; p++) {
         if (f.is_coupled(p)) continue;
-        if (any) {
-          std::fill(pts.begin(), pts.end(), 0.0);
-          for (int k = 0; k < f.len[p]; k++) {
-            const double *src = tracks + ((size_t)p * max_len + k) * M * 6;
-            double *dst = pts.data() + (size_t)k * PMAF_FTRACK_POINT;
-            for (int i = 0; i < M; i++)
-              for (int c = 0; c < 6; c++) dst[c * PMAF_FTRACK_LANES + i] = src[i * 6 + c];
-          }
-          h->upload(f.d_pts.get() + (size_t)p * f.stride * PMAF_FTRACK_POINT, pts.data(), pts.size());
+        std::fill(pts.begin(), pts.end(), 0.0);
+        for (int k = 0; k < f.len[p]; k++) {
+          const double *src = tracks + ((size_t)p * max_len + k) * M * 6;
+          double *dst = pts.data() + (size_t)k * PMAF_FTRACK_POINT;
+          for (int i = 0; i < M; i++)
+            for (int c = 0; c < 6; c++) dst[c * PMAF_FTRACK_LANES + i] = src[i * 6 + c];
         }
-        h->upload(f.d_len.get() + p, &f.len[p], 1);
-        h->upload(f.d_first.get() + p, &zero, 1);
+        h->upload(f.d_pts.get() + (size_t)p * f.stride * PMAF_FTRACK_POINT, pts.data(), pts.size());
       }
+      upload_ftrack_lens(h);
       return;
     }
-    if (!any) {
-      set_tracked(h, false, "pmaf_set_obstacle_tracks", FIELD_TRACKS);
-      if (f.d_len.get()) {   // (the getter reads them)
-        h->upload(f.d_len.get(), f.len.data(), (size_t)P);
-        h->upload(f.d_first.get(), f.first.data(), (size_t)P);
-      }
-      return;
-    }
-    for (int p = 0; p < P; p++) f.len[p] = len[p];
     // the device layout (pmaf_ftrack.hpp): [P][stride][6][64], transposed here; a population's points lie at its own
     // stride, so a shorter upload into a grown buffer leaves the tail of the longer one behind it, never read
     if (f.d_pts.reserve(sizeof(double) * (size_t)P * std::max(f.stride, (int)max_len) * PMAF_FTRACK_POINT)) f.stride = std::max(f.stride, (int)max_len);
@@ -908,8 +947,120 @@ int pmaf_set_obstacle_tracks(pmaf_planner *h, const double *tracks, const int32_
           for (int c = 0; c < 6; c++) dst[c * PMAF_FTRACK_LANES + i] = src[i * 6 + c];
       }
     h->upload(f.d_pts.get(), pts.data(), pts.size());
-    h->upload(f.d_len.get(), f.len.data(), (size_t)P);
-    h->upload(f.d_first.get(), f.first.data(), (size_t)P);
+    upload_ftrack_lens(h);
+  });
+}
+
+// The memory a device source names, as the handle's device reads it -- decided before anything is enqueued: a kernel
+// that reads what the device cannot map faults, and a shared machine pays for that. `bytes`: from d_tracks to the end
+// of the last element that will be read.
+static const void *readable_source(pmaf_planner *h, const void *d_tracks, size_t bytes, const std::string &who) {
+  hipPointerAttribute_t a{};
+  const hipError_t e = hipPointerGetAttributes(&a, d_tracks);
+  if (e != hipSuccess) {   // (runtimes that do not know the pointer at all say so with an error)
+    (void)hipGetLastError();
+    fail(PMAF_ERR_INVALID, who + ": d_tracks is not memory the runtime knows (pageable host memory? copy it with pmaf_set_obstacle_tracks)");
+  }
+  const void *src = d_tracks;
+  switch (a.type) {
+    case hipMemoryTypeDevice:
+      if (a.device != h->device) {
+        // Readable only where the CALLER has enabled peer access from the handle's device (the current one). The runtime
+        // answers that question in one way: enabling it again says "already enabled". Where it was not, the call has
+        // just enabled it: that is taken back at once, and the source is refused -- the process's device state is the
+        // caller's to change.
+        int can = 0;
+        HIP_CHECK(hipDeviceCanAccessPeer(&can, h->device, a.device));
+        hipError_t pe = can ? hipDeviceEnablePeerAccess(a.device, 0) : hipErrorInvalidDevice;
+        if (pe == hipSuccess) (void)hipDeviceDisablePeerAccess(a.device);
+        (void)hipGetLastError();
+        if (pe != hipErrorPeerAccessAlreadyEnabled)
+          fail(PMAF_ERR_INVALID, who + ": d_tracks lies on device " + std::to_string(a.device) + ", to which the handle's device " +
+               std::to_string(h->device) + " has no peer access enabled (hipDeviceEnablePeerAccess is the caller's to call)");
+      }
+      break;
+    case hipMemoryTypeHost:      // pinned or registered: the device reads it through its alias
+      if (a.devicePointer) src = a.devicePointer;
+      break;
+    case hipMemoryTypeManaged:
+      break;
+    default:                     // unregistered (pageable) host memory, arrays
+      fail(PMAF_ERR_INVALID, who + ": d_tracks is not memory the handle's device can read (pageable host memory? copy it with pmaf_set_obstacle_tracks)");
+  }
+  // where the runtime can tell: the last element read lies inside the allocation
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(src)) == hipSuccess && base && size) {
+    const char *lo = static_cast<const char *>(base), *at = static_cast<const char *>(src);
+    if (at < lo || bytes > size || (size_t)(at - lo) > size - bytes)
+      fail(PMAF_ERR_INVALID, who + ": the tracks to be read (" + std::to_string(bytes) + " bytes) run past the end of d_tracks' allocation");
+  } else {
+    (void)hipGetLastError();
+  }
+  return src;
+}
+
+int pmaf_set_obstacle_tracks_device(pmaf_planner *h, const void *d_tracks, const int32_t *len, int32_t max_len,
+                                    int32_t components, int32_t dtype, void *producer_stream) {
+  return guarded([&] {
+    const char *who = "pmaf_set_obstacle_tracks_device";
+    REQUIRE(h, "pmaf_set_obstacle_tracks_device: NULL handle");
+    h->use_device();
+    require_drained(h, who);
+    REQUIRE(d_tracks && len, "pmaf_set_obstacle_tracks_device: NULL argument (detaching is pmaf_set_obstacle_tracks(h, NULL, NULL, 0))");
+    REQUIRE(components == 6 || components == 3, "pmaf_set_obstacle_tracks_device: components must be 6 or 3");
+    REQUIRE(dtype == PMAF_TRACK_F64 || dtype == PMAF_TRACK_F32, "pmaf_set_obstacle_tracks_device: unknown dtype (PMAF_TRACK_F64, PMAF_TRACK_F32)");
+    const size_t esz = dtype == PMAF_TRACK_F64 ? sizeof(double) : sizeof(float);
+    REQUIRE(((uintptr_t)d_tracks & (esz - 1)) == 0, "pmaf_set_obstacle_tracks_device: d_tracks is not aligned to its element type");
+    pmaf_planner::FieldTrack &f = h->ftrk;
+    const int P = h->D.P, M = h->D.n_obs - 1;
+    const bool any = ftrack_lens(h, len, max_len, who, [](int) {});
+    if (!any) {
+      sync(h);
+      detach_uploaded_ftracks(h, who);
+      return;
+    }
+    size_t bytes = 0;   // ... to the end of the last population's last point
+    for (int p = 0; p < P; p++)
+      if (len[p] > 0) bytes = ((size_t)p * max_len + (size_t)len[p]) * M * components * esz;
+    const void *src = readable_source(h, d_tracks, bytes, who);
+    check_tracked(h, who, FIELD_TRACKS);
+    sync(h);   // a running rollout still reads the buffers
+    // nothing a refusal would have to undo: buffers that exist, a buffer that grew with what it held
+    reserve_ftrack_aux(h);
+    f.d_in_len.reserve(sizeof(int32_t) * P);
+    f.d_verdict.reserve(sizeof(unsigned long long));
+    grow_ftrack_keeping(h, std::max(f.stride, (int)max_len));
+    std::vector<int32_t> in((size_t)P);
+    for (int p = 0; p < P; p++) in[p] = f.is_coupled(p) ? -1 : len[p];
+    // (no wait of its own: `in` lives until the verdict's copy has been waited for, behind both kernels)
+    HIP_CHECK(hipMemcpyAsync(f.d_in_len.get(), in.data(), sizeof(int32_t) * in.size(), hipMemcpyHostToDevice, h->stream));
+    if (producer_stream) {   // everything enqueued there up to now, without a word to the host
+      hipEvent_t ev = nullptr;
+      HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(producer_stream));
+      if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ev, 0);
+      (void)hipEventDestroy(ev);   // (released once the record has completed)
+      HIP_CHECK(e);
+    }
+    HIP_CHECK(hipMemsetAsync(f.d_verdict.get(), 0xFF, sizeof(unsigned long long), h->stream));
+    const FtIngestArgs A{src, f.d_in_len.get(), f.d_pts.get(), f.d_verdict.get(), (int)max_len, f.stride, M, h->D.C.dt};
+    pmaf_k_launch_ftingest(A, P, components, dtype, h->stream);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long key = 0;
+    h->download(&key, f.d_verdict.get(), 1);   // (waits for both kernels: the source may be overwritten from here on)
+    if (key != PMAF_FTINGEST_CLEAN) {
+      // the key's order: [P][max_len][M][6]
+      const int c = (int)(key % 6), i = (int)(key / 6 % (unsigned long long)M);
+      const unsigned long long pk = key / 6 / (unsigned long long)M;
+      fail(PMAF_ERR_INVALID, std::string(who) + ": tracks: population " + std::to_string(pk / (unsigned long long)max_len) + ", point " +
+           std::to_string(pk % (unsigned long long)max_len) + ", obstacle " + std::to_string(i) + ", component " + std::to_string(c) +
+           (components == 3 && c >= 3 ? " (the velocity derived from this point and the next)" : "") +
+           ": value outside the supported numeric range (finite, 0 or 2^-100 <= |x| <= 2^100)");
+    }
+    set_tracked(h, true, who, FIELD_TRACKS);
+    book_ftrack_lens(h, len);
+    upload_ftrack_lens(h);
   });
 }
 

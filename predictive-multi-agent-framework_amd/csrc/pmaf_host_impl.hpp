@@ -24,6 +24,7 @@
 #include "pmaf_track.hpp"
 #include "pmaf_ftrack.hpp"
 #include "pmaf_fcouple.hpp"
+#include "pmaf_ftingest.hpp"
 
 using namespace pmaf;
 
@@ -85,6 +86,10 @@ class GrowBuf {
     HIP_CHECK(PINNED ? hipHostMalloc((void **)&p_, bytes, hipHostMallocDefault) : hipMalloc((void **)&p_, bytes));
     bytes_ = bytes;
     return true;
+  }
+  void swap(GrowBuf &o) {   // (a buffer that grows and keeps its contents: filled beside the old one, then exchanged)
+    std::swap(p_, o.p_);
+    std::swap(bytes_, o.bytes_);
   }
 };
 template <typename T> using DeviceBuf = GrowBuf<T, false>;
@@ -299,6 +304,10 @@ struct pmaf_planner {
     int shift = 0;
     DeviceBuf<int32_t> d_src, d_is_src, d_sel_n;  // [P][64], [P], [P]
     DeviceBuf<double> d_scale, d_anchor, d_sel_pts;   // [P][64], [P][3][64], [P][cap][3]
+    // the device-memory source (pmaf_set_obstacle_tracks_device, pmaf_ftingest.hpp): the call's lengths as its kernels
+    // read them and the verdict word of its range check; scratch of the call, nothing the rollouts read
+    DeviceBuf<int32_t> d_in_len;                  // [P]
+    DeviceBuf<unsigned long long> d_verdict;      // one word
     bool is_coupled(int p) const { return coupled && pop_coupled[(size_t)p] != 0; }
     bool on() const { return attached || coupled; }
   } ftrk;

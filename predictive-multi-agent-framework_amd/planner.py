@@ -85,6 +85,7 @@ SYMBOLS = {
     "pmaf_set_obstacle_track_offset": (C.c_int, [_V, _ip]),
     "pmaf_get_obstacle_tracks": (C.c_int, [_V, _dp, _ip, _ip, C.c_int32]),
     "pmaf_couple_obstacle_tracks": (C.c_int, [_V, _ip, _dp, _dp, C.c_int32]),
+    "pmaf_set_obstacle_tracks_device": (C.c_int, [_V, _V, _ip, C.c_int32, C.c_int32, C.c_int32, _V]),
     "pmaf_evaluate_paths_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, _dp, _ip, _ip, _ip, _dp]),
     "pmaf_select_clear_tracked": (C.c_int, [_V, _dp, _ip, C.c_double, C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _ip, _ip, _dp,
                                             _dp, _ip]),
@@ -841,6 +842,58 @@ class PmafPlanner:
             for p, t in enumerate(tr):
                 buf[p, :len(t)] = t
         self._chk(self.L.pmaf_set_obstacle_tracks(self._h, _p(buf), _pi(ln), int(buf.shape[1])))
+
+    TRACK_F64, TRACK_F32 = 0, 1
+
+    @staticmethod
+    def _track_dtype(dtype):
+        """PMAF_TRACK_F64 / PMAF_TRACK_F32 from the constant itself or from a dtype by its name (numpy's, torch's: the
+        package does not import torch); ValueError for anything else"""
+        if isinstance(dtype, (int, np.integer)) and not isinstance(dtype, bool):
+            return int(dtype)   # (a constant the library does not know is the library's to refuse)
+        name = str(getattr(dtype, "name", dtype)).rsplit(".", 1)[-1]
+        if name == "float64":
+            return PmafPlanner.TRACK_F64
+        if name == "float32":
+            return PmafPlanner.TRACK_F32
+        raise ValueError("set_obstacle_tracks_device: the tracks must be float64 or float32, not %s" % (dtype,))
+
+    def set_obstacle_tracks_device(self, src, lengths=None, *, components=None, dtype=None, max_len=None, producer_stream=None):
+        """the obstacle tracks from memory the device reads (pmaf_set_obstacle_tracks_device). src: an integer device
+        pointer with explicit dtype / max_len / components, or any object with data_ptr(), dtype, shape and
+        is_contiguous() -- a torch tensor on the handle's device --, [P][max_len][M][c] or, for a single population,
+        [L][M][c]; c = 6 (position and velocity) or 3 (positions: the velocities are their forward differences over dt).
+        lengths [P]: the points per population (default: max_len for all). producer_stream: the integer handle of the
+        stream the tensor was written on (torch.cuda.current_stream().cuda_stream), or None when the data is complete.
+        What a tensor cannot be handed over as it is -- another dtype, non-contiguous, another shape -- is a ValueError
+        here, in front of the C call."""
+        M = self.n_obs - 1
+        if hasattr(src, "data_ptr"):
+            code = self._track_dtype(src.dtype)
+            if dtype is not None and self._track_dtype(dtype) != code:
+                raise ValueError("set_obstacle_tracks_device: dtype does not match the tensor's (%s)" % (src.dtype,))
+            if not src.is_contiguous():
+                raise ValueError("set_obstacle_tracks_device: the tensor must be contiguous")
+            shape = tuple(int(n) for n in src.shape)
+            if len(shape) == 3 and self.P == 1:
+                shape = (1,) + shape
+            if len(shape) != 4 or shape[0] != self.P or shape[2] != M or shape[3] not in (3, 6) or shape[1] < 1:
+                raise ValueError("set_obstacle_tracks_device: the tensor must be [P=%d][max_len >= 1][M=%d][3 or 6]%s, not %s"
+                                 % (self.P, M, " (or [L][M][c])" if self.P == 1 else "", tuple(src.shape)))
+            if components is not None and int(components) != shape[3]:
+                raise ValueError("set_obstacle_tracks_device: components does not match the tensor's last axis (%d)" % shape[3])
+            if max_len is not None and int(max_len) != shape[1]:
+                raise ValueError("set_obstacle_tracks_device: max_len does not match the tensor's (%d)" % shape[1])
+            ptr, max_len, components = int(src.data_ptr()), shape[1], shape[3]
+        else:
+            if isinstance(src, bool) or not isinstance(src, (int, np.integer)):
+                raise ValueError("set_obstacle_tracks_device: src is neither a device pointer nor an object with data_ptr()")
+            if dtype is None or max_len is None or components is None:
+                raise ValueError("set_obstacle_tracks_device: a raw pointer needs dtype, max_len and components")
+            ptr, code, max_len, components = int(src), self._track_dtype(dtype), int(max_len), int(components)
+        ln = np.ascontiguousarray(np.broadcast_to(np.asarray(max_len if lengths is None else lengths, dtype=np.int32), (self.P,)))
+        stream = None if producer_stream is None else C.c_void_p(int(producer_stream))
+        self._chk(self.L.pmaf_set_obstacle_tracks_device(self._h, C.c_void_p(ptr), _pi(ln), int(max_len), int(components), code, stream))
 
     def set_obstacle_track_offset(self, first):
         """first: [P] (or one number for all): the point of the tracks prediction step 0 reads"""
