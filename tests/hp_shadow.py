@@ -189,20 +189,43 @@ def check_real(A, st, scene, pre, post, init_pos, obs_rows, best):
     st.run(A, real)
 
 
-def check_rollouts(A, st, scene, pos, vel, known, pre_rot, pre_success, post, obs_rows, init_pos, agents):
+def _reference_rollout(A, scene, i, pos, vel, known, rot_i, obs_rows, init_pos, memo):
+    """the reference's rollout of agent i from exact inputs: (agent, ran). memo: a dict shared between planners that are
+    shadowed on the same scene -- the reference is a function of the inputs' bits and the policy's two parameters alone,
+    so it is computed once per distinct input (a rollout that is undecidable raises again, the decided branches return)"""
+    def compute():
+        a = hp.Agent(A, pos, (0.0, 0.0, 0.0), scene["goal"], init_pos, known, rot_i, atype=agent_types(scene)[i],
+                     rand_vecs=scene["random_vecs"][i], **_params(scene))
+        hp.set_velocity(A, a, vel)
+        own = hp.obstacles_from_rows(A, obs_rows, radii=scene["obstacles"][:, 6])
+        ran = hp.prediction(A, a, own, _gains(scene, i), scene["dt"], int(scene["max_prediction_steps"]))
+        return a, ran
+    if memo is None:
+        return compute()
+    prm = _params(scene)
+    key = (A.eps, A.exact_divsqrt, agent_types(scene)[i], int(scene["max_prediction_steps"])) + tuple(
+        np.ascontiguousarray(x, dtype=np.float64).tobytes() for x in (
+            pos, vel, np.asarray(known, dtype=bool), rot_i, obs_rows, init_pos, scene["goal"], scene["random_vecs"][i],
+            scene["obstacles"][:, 6], _gains(scene, i), scene["dt"], [prm[k] for k in sorted(prm)]))
+    if key not in memo:
+        try:
+            memo[key] = compute() + (dict(A.seen),)
+        except hp.Undecidable as e:
+            memo[key] = e
+    if isinstance(memo[key], hp.Undecidable):
+        raise memo[key]
+    a, ran, seen = memo[key]
+    A.seen = {k: set(v) for k, v in seen.items()}
+    return a, ran
+
+
+def check_rollouts(A, st, scene, pos, vel, known, pre_rot, pre_success, post, obs_rows, init_pos, agents, memo=None):
     """resetEEAgents(pos, vel, obstacles) with the real agent's known flags (B/src/cf_manager.cpp:246-255), then every
     sampled agent's cfPrediction to its guard (capacity max_prediction_steps, B/src/cf_agent.cpp:302-341); its private
-    obstacle copy keeps the radii it was constructed with (B/src/cf_agent.cpp:63-70)"""
-    types = agent_types(scene)
-    radii0 = scene["obstacles"][:, 6]
-    cap = int(scene["max_prediction_steps"])
+    obstacle copy keeps the radii it was constructed with (B/src/cf_agent.cpp:63-70). memo: see _reference_rollout"""
     for i in agents:
         def roll(i=i):
-            a = hp.Agent(A, pos, (0.0, 0.0, 0.0), scene["goal"], init_pos, known, pre_rot[i], atype=types[i],
-                         rand_vecs=scene["random_vecs"][i], **_params(scene))
-            hp.set_velocity(A, a, vel)
-            own = hp.obstacles_from_rows(A, obs_rows, radii=radii0)
-            ran = hp.prediction(A, a, own, _gains(scene, i), scene["dt"], cap)
+            a, ran = _reference_rollout(A, scene, i, pos, vel, known, pre_rot[i], obs_rows, init_pos, memo)
             n = int(post["n"][i])
             st.expect("n_points[%d]" % i, len(a.path), n)
             for k in range(1, min(len(a.path), n)):

@@ -70,10 +70,12 @@ def _moving_rel(s, e, tick, k):
     return c0 - H * tick - 2.0 * H * k
 
 
-def build_scene(scenes, name, moving=False, sent_near=False):
+def build_scene(scenes, name, moving=False, sent_near=False, n_agents=N_AGENTS):
     """scenes: the package's scenes module. moving (the bodies that advance the obstacles): "cluster" -- the last cluster
     flies head-on; "far" -- a far obstacle moves away and K is what it is at rest. sent_near: the repulsive obstacle
-    stands 0.6 m beside the third lattice point, in repelForce's range for most of the rollout, instead of 170 m away."""
+    stands 0.6 m beside the third lattice point, in repelForce's range for most of the rollout, instead of 170 m away.
+    n_agents: a larger population (more waves than SIMDs) -- the seven types repeated, the random vectors drawn in the
+    same order, so agents 0 ... 6 are the default call's agents (tests/test_variant_matrix.py asserts it)."""
     spec = SCENES[name]
     rng = np.random.default_rng(5200 + sorted(SCENES).index(name))
     rows = []
@@ -103,14 +105,16 @@ def build_scene(scenes, name, moving=False, sent_near=False):
     else:
         rows.append([100.0, 100.0, 100.0, 0.0, 0.0, 0.0, SENT_RADIUS])
     obs = np.asarray(rows, dtype=np.float64)
-    rv = rng.uniform(-1.0, 1.0, (N_AGENTS, M + 1, 3))
+    assert n_agents >= N_AGENTS
+    rv = rng.uniform(-1.0, 1.0, (n_agents, M + 1, 3))
     rv /= np.linalg.norm(rv, axis=-1, keepdims=True)
+    types = np.resize(scenes.default_agent_types(N_AGENTS), n_agents)
     return dict(name="long_loop_%s%s%s" % (name, ("_" + moving) if moving else "", "_sent" if sent_near else ""),
-                n_agents=N_AGENTS, max_prediction_steps=spec["cap"], dt=DT, velocity_max=VMAX, approach_dist=0.25,
+                n_agents=n_agents, max_prediction_steps=spec["cap"], dt=DT, velocity_max=VMAX, approach_dist=0.25,
                 detect_shell_rad=SHELL, agent_mass=1.0, radius=RAD, k_attr=5.0, k_circ=0.01, k_repel=0.002, k_damp=5.0,
                 cost_gains=np.array([100.0, 10.0, 0.001, 1.0]), ws_limits=np.array([40.0, -10.0, 3.0, -3.0, 3.0, -2.0]),
                 start=START.copy(), goal=GOAL.copy(), obstacles=obs, random_vecs=rv,
-                agent_types=scenes.default_agent_types(N_AGENTS))    # Had, Goal, Obstacle, GoalObstacle, Vel, Random x 2
+                agent_types=types)    # Had, Goal, Obstacle, GoalObstacle, Vel, Random x 2 (repeated)
 
 
 def cases():

@@ -86,9 +86,10 @@ def reference(oracle, scenes, name, moving, sent_near, ftracks=None, track=None)
     return _REF[key]
 
 
-def run_and_compare(pmaf, sc, ticks, final_costs, P=1, setup=None, expect_sliced=False, tag=""):
+def run_and_compare(pmaf, sc, ticks, final_costs, P=1, setup=None, expect_sliced=False, tag="", planner_kw=None):
+    """planner_kw: further keyword arguments of PmafPlanner (the arithmetic policy: tests/variant_matrix.py)"""
     scenes_arg = sc if P == 1 else [sc] * P
-    pl = pmaf.PmafPlanner(scenes_arg, device=0, mgr_init_pos=np.tile(lls.INIT, (P, 1)))
+    pl = pmaf.PmafPlanner(scenes_arg, device=0, mgr_init_pos=np.tile(lls.INIT, (P, 1)), **(planner_kw or {}))
     try:
         pl.set_real_position(np.tile(lls.START, (P, 1)))
         cfg = pl.launch_config()
@@ -138,13 +139,18 @@ def test_k_varies_with_a_repulsive_track(pmaf, oracle, scenes, name):
     run_and_compare(pmaf, sc, ticks, costs, setup=setup, tag="%s repulsive track" % name)
 
 
+def _obstacle_tracks(sc0):
+    """a track per field obstacle, 2 mm beside its live position and drifting 0.5 mm per point"""
+    ft = fref.straight_lines(sc0["obstacles"], sc0["dt"], sc0["max_prediction_steps"] + 2)
+    ft[:, :, 0:3] += np.array([0.0, 0.002, -0.001])[None, None, :] + np.arange(len(ft))[:, None, None] * 0.0005
+    return ft
+
+
 @pytest.mark.parametrize("name", sorted(lls.SCENES))
 def test_k_varies_with_obstacle_tracks(pmaf, oracle, scenes, name):
     """every field obstacle follows a track 2 mm beside its live position, drifting 0.5 mm per point: far inside the
     scenes' margins, K stays what it is (k_rollout_w64_ftrack)"""
-    sc0 = lls.build_scene(scenes, name, False, False)
-    ft = fref.straight_lines(sc0["obstacles"], sc0["dt"], sc0["max_prediction_steps"] + 2)
-    ft[:, :, 0:3] += np.array([0.0, 0.002, -0.001])[None, None, :] + np.arange(len(ft))[:, None, None] * 0.0005
+    ft = _obstacle_tracks(lls.build_scene(scenes, name, False, False))
     sc, ticks, costs = reference(oracle, scenes, name, False, False, ftracks=ft)
     plain = reference(oracle, scenes, name, False, False)[1]
     assert not np.array_equal(ticks[-1][1]["paths"], plain[-1][1]["paths"])        # the tracks matter

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import sum_chunk_scenes as scs
+import variant_matrix as vm
 
 
 @pytest.fixture(autouse=True)
@@ -33,7 +34,21 @@ def _placement(sc, K):
 
 @pytest.mark.parametrize("K,moving,sent_near", scs.cases())
 def test_first_step_has_k_terms(oracle, scenes, K, moving, sent_near):
-    sc = scs.build_scene(scenes, K, moving, sent_near)
+    _holds_k(oracle, scs.build_scene(scenes, K, moving, sent_near), K, moving, sent_near)
+
+
+@pytest.mark.parametrize("variant", vm.GENERAL_VARIANTS)
+@pytest.mark.parametrize("moving,sent_near", vm.SUM_CHUNK_STRICT_FLAGS)
+@pytest.mark.parametrize("K", vm.GENERAL_KS)
+def test_k_is_held_with_inputs_that_need_the_general_step(oracle, scenes, K, moving, sent_near, variant):
+    """agent_mass = 2.5, and k_attr = 0 for agents 1 and 4 on top (tests/variant_matrix.py general_scene): other
+    dynamics on the same obstacles -- the margins still hold K at every step of every tick"""
+    sc = vm.general_scene(scs.build_scene(scenes, K, moving, sent_near), variant)
+    assert sc["agent_mass"] == 2.5 and (np.ndim(sc["k_attr"]) == 1) == (variant == "mass_noattr")
+    _holds_k(oracle, sc, K, moving, sent_near)
+
+
+def _holds_k(oracle, sc, K, moving, sent_near):
     assert sc["obstacles"].shape == (scs.M + 1, 7) and sc["n_agents"] == scs.N_AGENTS == 7
     assert sorted(set(sc["agent_types"].tolist())) == [1, 2, 3, 4, 5, 6] and (sc["agent_types"] == 5).sum() == 2
     assert bool(sc["obstacles"][:-1, 3:6].any()) == moving

@@ -42,15 +42,18 @@ def _state(pl, sc):
 _REF = {}
 
 
-def reference(oracle, scenes, K, moving, sent_near, ftracks=None, track=None):
+def reference(oracle, scenes, K, moving, sent_near, ftracks=None, track=None, edit=None):
     """per tick (best index, results) of the oracle: computed once per case, shared, never modified. With tracks the
     rollout of a tick is the composed one of the track references (select, real step against the live list, reset,
     rollout against the tracks: tests/sentinel_track_reference.py coupled_ticks, tests/field_track_reference.py
-    tracked_ticks)."""
-    key = (K, moving, sent_near, ftracks is not None, track is not None)
+    tracked_ticks). edit: (tag, function) -- the scene is function(scene) (other dynamics on the same obstacles:
+    tests/variant_matrix.py general_scene), the reference its own."""
+    key = (K, moving, sent_near, ftracks is not None, track is not None, edit[0] if edit else None)
     if key in _REF:
         return _REF[key]
     sc = scs.build_scene(scenes, K, moving, sent_near)
+    if edit:
+        sc = edit[1](sc)
     ora = oracle.OraclePlanner(sc, mgr_init_pos=scs.INIT)
     scs.prepare(ora)
     ticks = []
@@ -83,9 +86,10 @@ def reference(oracle, scenes, K, moving, sent_near, ftracks=None, track=None):
     return _REF[key]
 
 
-def run_and_compare(pmaf, sc, ticks, final_costs, P=1, setup=None, expect_sliced=False, tag=""):
+def run_and_compare(pmaf, sc, ticks, final_costs, P=1, setup=None, expect_sliced=False, tag="", planner_kw=None):
+    """planner_kw: further keyword arguments of PmafPlanner (the arithmetic policy: tests/variant_matrix.py)"""
     scenes_arg = sc if P == 1 else [sc] * P
-    pl = pmaf.PmafPlanner(scenes_arg, device=0, mgr_init_pos=np.tile(scs.INIT, (P, 1)))
+    pl = pmaf.PmafPlanner(scenes_arg, device=0, mgr_init_pos=np.tile(scs.INIT, (P, 1)), **(planner_kw or {}))
     try:
         pl.set_real_position(np.tile(scs.START, (P, 1)))
         cfg = pl.launch_config()
@@ -116,10 +120,20 @@ def test_k_terms_three_ticks(pmaf, oracle, scenes, K, moving, sent_near):
     run_and_compare(pmaf, sc, ticks, costs, tag="K%d moving=%s sent=%s" % (K, moving, sent_near))
 
 
+def _track():
+    return scs.START[None, :] + np.array([-0.05, 0.3, 0.0])[None, :] + np.arange(scs.CAP + 2)[:, None] * np.array([0.004, -0.002, 0.001])[None, :]
+
+
+def _obstacle_tracks(sc0):
+    ft = fref.straight_lines(sc0["obstacles"], sc0["dt"], scs.CAP + 2)
+    ft[:, :, 0:3] += np.array([0.0, 0.002, -0.001])[None, None, :] + np.arange(len(ft))[:, None, None] * 0.0005
+    return ft
+
+
 @pytest.mark.parametrize("K", scs.TRACK_KS)
 def test_k_terms_with_a_repulsive_track(pmaf, oracle, scenes, K):
     """the tracked repulsive obstacle passes 0.3 m beside the agents, in repelForce's range (k_rollout_w64_track)"""
-    track = scs.START[None, :] + np.array([-0.05, 0.3, 0.0])[None, :] + np.arange(scs.CAP + 2)[:, None] * np.array([0.004, -0.002, 0.001])[None, :]
+    track = _track()
     sc, ticks, costs = reference(oracle, scenes, K, False, True, track=track)
     plain = reference(oracle, scenes, K, False, True)[1]
     assert not np.array_equal(ticks[-1][1]["paths"], plain[-1][1]["paths"])        # the track matters
@@ -132,9 +146,7 @@ def test_k_terms_with_a_repulsive_track(pmaf, oracle, scenes, K):
 @pytest.mark.parametrize("K", scs.TRACK_KS)
 def test_k_terms_with_obstacle_tracks(pmaf, oracle, scenes, K):
     """every field obstacle follows a track 2 mm beside its live position, drifting (k_rollout_w64_ftrack)"""
-    sc0 = scs.build_scene(scenes, K, False, False)
-    ft = fref.straight_lines(sc0["obstacles"], sc0["dt"], scs.CAP + 2)
-    ft[:, :, 0:3] += np.array([0.0, 0.002, -0.001])[None, None, :] + np.arange(len(ft))[:, None, None] * 0.0005
+    ft = _obstacle_tracks(scs.build_scene(scenes, K, False, False))
     sc, ticks, costs = reference(oracle, scenes, K, False, False, ftracks=ft)
     plain = reference(oracle, scenes, K, False, False)[1]
     assert not np.array_equal(ticks[-1][1]["paths"], plain[-1][1]["paths"])        # the tracks matter
